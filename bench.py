@@ -1,6 +1,6 @@
 """Training-step throughput of the open-vocabulary 3DETR hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 One step = forward (3DETR: FPS + ball query + grouping [HIP], SA-MLP,
@@ -10,11 +10,23 @@ on a fresh synthetic SUN RGB-D-like batch (B=8 scenes x 20000 points per GPU,
 nqueries=128, text embedding 21x640) already resident in HBM.  BASELINE.json
 metric: scenes/sec (train step); weak scaling (8 scenes per GPU), DDP over RCCL.
 
-Rank 0 prints ONE JSON line.  It carries a `roofline` object for the dominant
-hand-written kernel (ov3d_fps, timed with HIP events on its launch stream; inside
-the timed region in eager mode, right after it when the step replays a hipGraph) and a `cpu_baseline` (the CPU port of the same step: the
-oracle's C restatement for the index kernels + PyTorch-CPU dense layers, a
-bounded sample, rank 0 only, N=1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps
+and prints the headline figures (`value`, `ms_per_step`, ...), nothing else.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step
+computed as DIR/<name>.npy (float32): `loss` (what the step returns), `params`
+(every trainable parameter after the step's update, flattened in
+model.parameters() order) and `grads` (the step's parameter gradients in the same
+order, as the optimizer left them; zeros where a parameter has none).  An array over its share of
+the 48 MB budget is written as a fixed sample (numpy PCG64, seed 0, sorted
+positions).  The inputs are seeded, so two builds can be compared array for array.
+
+--full adds the measurements that take runs of their own: a `roofline` object for
+the dominant hand-written kernel (in-kernel stamps of the captured step's launches,
+read over the last timed step + 5 more replays, and a standalone relaunch), the
+backward attention, FPS and index-kernel figures, the measured GEMM ceiling, and a
+`cpu_baseline` (the CPU port of the same step: the oracle's C restatement for the
+index kernels + PyTorch-CPU dense layers, a bounded sample, rank 0 only, N=1 only).
 """
 import argparse
 import json
@@ -379,6 +391,27 @@ def cpu_baseline(args, rounds=5, b8_steps=2):
                        "PyTorch-CPU dense layers; value: B=1 scenes / median step time")}
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # all dumped arrays together (float32)
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files (module
+    docstring).  Call right after the timed region: later replays overwrite the step's buffers."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays = {"loss": loss.detach().reshape(1),
+              "params": torch.cat([p.detach().reshape(-1).float() for p in params])}
+    arrays["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p))
+                                 .detach().reshape(-1).float() for p in params])
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES // 4 - 1) // 2   # elements: the loss, then params and grads alike
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        if a.size > share:   # the same positions of both
+            pick = np.random.Generator(np.random.PCG64(0)).choice(a.size, size=share, replace=False)
+            a = a[np.sort(pick)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -389,7 +422,14 @@ def main():
     p.add_argument("--batch", type=int, default=None, help="scenes per GPU (default: workload's)")
     p.add_argument("--points", type=int, default=None, help="points per scene (default: workload's)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what takes runs of its own: the roofline and per-kernel "
+                        "figures and the CPU baseline (module docstring)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (loss, params, grads) as "
+                        "DIR/<name>.npy, float32")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--pool", type=int, default=4, help="distinct synthetic batches cycled")
     p.add_argument("--no-prefetch", action="store_true",
                    help="do not overlap the next batch's pre-encoder FPS with this step")
@@ -466,12 +506,16 @@ def main():
         from ov3d_amd.graphs import StepGraph
         # the encoder attention launches captured into the step carry in-kernel wall-clock
         # stamps (csrc/common.h ov3d_stamp): the roofline kernel is timed inside the step
-        # (armed after the eager warm-up, so the launch table holds the captured launches only)
-        stamp_buf = torch.zeros((1 << 21,), dtype=torch.int64, device=device)
+        # (armed after the eager warm-up, so the launch table holds the captured launches only).
+        # --full only: a plain run captures the step without stamps
+        arm = None
+        if cli.full:
+            stamp_buf = torch.zeros((1 << 21,), dtype=torch.int64, device=device)
+            arm = lambda: _native.stamps_arm(stamp_buf, min_work=1 << 20)  # noqa: E731
         try:
             graphed = StepGraph(model, crit, opt, pool[0], amp_dtype=amp, clip=args.clip_gradient,
                                 prefetch_fps=not cli.no_prefetch, regionclip=clip,
-                                before_capture=lambda: _native.stamps_arm(stamp_buf, min_work=1 << 20))
+                                before_capture=arm)
         finally:
             _native.stamps_arm(None)
 
@@ -485,7 +529,7 @@ def main():
     torch.cuda.synchronize()
     dist.barrier()
 
-    if graphed is None:
+    if graphed is None and cli.full:
         _native.timing_enable(["ov3d_fps"])
     torch.cuda.synchronize()
     dist.barrier()
@@ -498,6 +542,8 @@ def main():
     torch.cuda.synchronize()
     dist.barrier()
     elapsed = time.perf_counter() - t0
+    if cli.dump_outputs and rank == 0:
+        dump_outputs(cli.dump_outputs, loss, model)
     # in-step kernel times: the last timed step's captured launches, then 5 more replays
     stamped = []
     if stamp_buf is not None:
@@ -507,10 +553,12 @@ def main():
             step(cli.steps + i)
             torch.cuda.synchronize()
             stamped.append(_native.stamps_read(stamp_buf))
-    timings = _native.timing_collect() if graphed is None else fps_launch_timings(pool, cli)
+    timings = {}
+    if cli.full:
+        timings = _native.timing_collect() if graphed is None else fps_launch_timings(pool, cli)
     att = None
     rates = gemm_ref = None
-    if rank == 0 and dataset in ("sunrgbd", "scannet"):
+    if cli.full and rank == 0 and dataset in ("sunrgbd", "scannet"):
         att = attn_launch_timings(cli.batch, args.preenc_npoints, args.enc_nhead, args.enc_dropout)
         fps_floor_ms = fps_latency_floor(cli.batch, args.preenc_npoints)
         gemm_ref = gemm_ceiling()
@@ -646,7 +694,7 @@ def main():
     res = {
         "metric": metric,
         "value": round(value, 3), "unit": "scenes/s", "n_gpus": world, "steps": cli.steps,
-        "warmup": cli.warmup, "ms_per_step": round(elapsed / cli.steps * 1e3, 3),
+        "warmup": cli.warmup, "full": cli.full, "ms_per_step": round(elapsed / cli.steps * 1e3, 3),
         "ms_per_step_median": round(float(np.median(per_step)), 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": cli.dtype,
         "data": "synthetic SUN RGB-D-like scenes (numpy PCG64), random-init weights",
@@ -659,7 +707,9 @@ def main():
     }
     if dataset == "scannet":
         res["data"] = "synthetic ScanNet-like scenes (numpy PCG64, axis-aligned boxes), random-init weights"
-    if wl["use_image"]:
+    if not cli.full:
+        pass
+    elif wl["use_image"]:
         res["cpu_baseline"] = {"value": None, "note": "not run for C5: the RN50x4 ROI path is "
                                f"{regionclip_gflop_per_scene(cli.batch) / 1e3:.1f} TFLOP/scene"}
     elif world == 1 and not cli.no_cpu_baseline and dataset == "sunrgbd":

@@ -15,7 +15,7 @@ rc=$?; tail -3 $OUT/smoke.log; [ $rc -eq 0 ] || stop smoke $rc
 echo "== pytest -m gpu"; timeout -k 10 1000 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread > $OUT/pytest_gpu.log 2>&1
 rc=$?; tail -15 $OUT/pytest_gpu.log; if fatal $rc; then stop pytest $rc; fi
 
-echo "== bench"; timeout -k 10 600 python bench.py --steps ${STEPS:-20} --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+echo "== bench"; timeout -k 10 600 python bench.py --steps ${STEPS:-20} --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; cat $OUT/bench.json; tail -5 $OUT/bench.err; [ $rc -eq 0 ] || stop bench $rc
 
 if [ "${PROFILE:-1}" = "1" ]; then

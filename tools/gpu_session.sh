@@ -20,7 +20,7 @@ for step in "$@"; do
       timeout -k 10 1500 python -u -m pytest ${TESTS:-tests -m gpu} -x -q --timeout 300 --timeout-method thread > $O/${T}_pytest.log 2>&1 || fail tests $? $O/${T}_pytest.log
       tail -2 $O/${T}_pytest.log ;;
     bench)
-      timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $O/${T}_bench.json 2> $O/${T}_bench.err || fail bench $? $O/${T}_bench.err
+      timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $O/${T}_bench.json 2> $O/${T}_bench.err || fail bench $? $O/${T}_bench.err
       python -c "import json; d=json.load(open('$O/${T}_bench.json')); r=d.get('roofline') or {}; print('SUN', d['value'], d['ms_per_step_median'], r.get('frac'), (d.get('cpu_baseline') or {}).get('value'))" ;;
     quick)
       for rep in 1 2; do

@@ -541,6 +541,35 @@ int ov3d_lngemm_bwd(int R, const float* s, const float* mean, const float* rstd,
                     const void* W, long long ldw, int N, int epilogue, float dropout_p2,
                     const void* H, long long ldh, void* dx, long long lddx, void* stream);
 
+/* The encoder layer's row-local chain after its self-attention in one launch each way
+ * (csrc/encpost.hip) [models/transformer.py TransformerEncoderLayer.forward_pre 262-280]:
+ * C = 256, F = 128 (ov3d_enc_post_supported: also R % 64 == 0), contiguous rows, bf16 weights
+ * and biases (all three required), 16-byte aligned operands, ldw % 8 == 0.
+ * ov3d_enc_post_fwd: y1 = bf16(o Wo^T + bo) (not stored); s1 = s + dropout_p1(y1) (site1);
+ * mean / rstd / x2 = bf16(LN(s1) g2 + be2); h = dropout_pf(relu(bf16(x2 W1^T + b1))) (site_ffn);
+ * y2 = bf16(h W2^T + b2).  Wo (256, 256), W1 (128, 256), W2 (256, 128) nn.Linear weight rows.
+ * ov3d_enc_post_bwd: d1 = h > 0 ? bf16(bf16(dy2 W2) / (1 - pf)) : 0; dx2 = bf16(d1 W1) (not
+ * stored); ds = ds1 + the LayerNorm input gradient of dx2; dy1 = bf16(dropout_p1(ds));
+ * dout = bf16(dy1 Wo); partials (nparts = ov3d_resnorm_bwd_parts(R, 256), 4, 256) as
+ * ov3d_resnorm_bwd writes them (the column sums are left to ov3d_colsum_group).
+ * The outputs equal, bit for bit, those of ov3d_tile_gemm / ov3d_resnorm_fwd /
+ * ov3d_tile_gemm_act (epilogue 1) / ov3d_tile_gemm and of their backward counterparts;
+ * k_quarters = 1: those of the ov3d_rows_gemm entries instead (K summed in four quarters),
+ * which the unfused path uses on short row blocks. */
+int ov3d_enc_post_supported(int R, int C, int F);
+int ov3d_enc_post_fwd(int R, const float* s, const void* o, const void* Wo, long long ldwo,
+                      const void* bo, float p1, const int64_t* seed, int site1, const float* g2,
+                      const float* be2, float eps, const void* W1, long long ldw1, const void* b1,
+                      float pf, int site_ffn, const void* W2, long long ldw2, const void* b2,
+                      int k_quarters, float* s1, float* mean, float* rstd, void* x2, void* h,
+                      void* y2, void* stream);
+int ov3d_enc_post_bwd(int R, const float* ds1, const void* dy2, const float* s1, const float* mean,
+                      const float* rstd, const void* h, const float* g2, const void* Wo,
+                      long long ldwo, const void* W1, long long ldw1, const void* W2,
+                      long long ldw2, float p1, const int64_t* seed, int site1, float pf,
+                      int k_quarters, float* ds, void* dy1, void* dout, void* d1, float* partials,
+                      int nparts, void* stream);
+
 /* ---- Flash attention (head_dim 64, bf16, no mask) ----
  * Replaces the nn.MultiheadAttention core of models/transformer.py:223,271 (encoder
  * self-attention) and :307-308,365-372 (decoder self / cross attention): per head

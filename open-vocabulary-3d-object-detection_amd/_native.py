@@ -130,6 +130,8 @@ _SIGS = {
     "ov3d_rows256": "pliiplpllpp",
     "ov3d_rows256_bn": "plppplplpllpp",
     "ov3d_lngemm_bwd": "ipppppppilllppfpipppipipliifplplp",
+    "ov3d_enc_post_fwd": "ippplpfpippfplpfiplpippppppp",
+    "ov3d_enc_post_bwd": "ipppppppplplplfpifipppppip",
 }
 EXPORTS = tuple(_SIGS) + ("ov3d_version", "ov3d_sa_layer_supported", "ov3d_attn_fwd_workspace",
                           "ov3d_attn_dropbits_words", "ov3d_attn_maskbits_words", "ov3d_fps_workspace", "ov3d_attn_small_bwd", "ov3d_set_loss_fwd_parts",
@@ -143,7 +145,8 @@ EXPORTS = tuple(_SIGS) + ("ov3d_version", "ov3d_sa_layer_supported", "ov3d_attn_
                           "ov3d_stamps_get", "ov3d_wall_clock_khz",
                           "ov3d_attnpool_fused_supported", "ov3d_lngemm_supported",
                           "ov3d_lngemm_bwd_parts", "ov3d_lngemm_stamps_arm", "ov3d_stream_create",
-                          "ov3d_ball_query_ws_bytes", "ov3d_rows256_supported")
+                          "ov3d_ball_query_ws_bytes", "ov3d_rows256_supported",
+                          "ov3d_enc_post_supported")
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_longlong, "f": ctypes.c_float,
        "d": ctypes.c_double}
@@ -224,6 +227,8 @@ def load():
         lib.ov3d_lngemm_bwd_parts.restype = ctypes.c_int
         lib.ov3d_lngemm_stamps_arm.argtypes = [ctypes.c_void_p]
         lib.ov3d_lngemm_stamps_arm.restype = ctypes.c_int
+        lib.ov3d_enc_post_supported.argtypes = [ctypes.c_int] * 3
+        lib.ov3d_enc_post_supported.restype = ctypes.c_int
         lib.ov3d_heads_out_workspace.argtypes = [ctypes.c_int] * 2
         lib.ov3d_heads_out_workspace.restype = ctypes.c_longlong
         lib.ov3d_stream_create.argtypes = [ctypes.c_void_p]

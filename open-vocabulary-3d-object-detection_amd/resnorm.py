@@ -658,6 +658,148 @@ def _bias(b):
     return b.contiguous() if b is not None else None
 
 
+# The encoder layer's chain after its self-attention (out-projection, residual + dropout, norm2,
+# linear1 -> ReLU -> dropout -> linear2) in one launch each way (csrc/encpost.hip).
+# OV3D_ENC_POST=0: the four launches each way; "fwd" / "bwd": only that direction fused.
+_ENC_POST = os.environ.get("OV3D_ENC_POST", "1")
+enc_post = _ENC_POST != "0"
+enc_post_fwd = _ENC_POST != "bwd"   # with enc_post: the forward on ov3d_enc_post_fwd
+enc_post_bwd = _ENC_POST != "fwd"   # with enc_post: the backward on ov3d_enc_post_bwd
+
+
+def _al16(t):
+    return t if (t.is_contiguous() and t.data_ptr() % 16 == 0) else t.contiguous().clone()
+
+
+class _EncPost(torch.autograd.Function):
+    """(s1, y2) of an encoder layer from its residual stream s (fp32) and attention output o:
+        s1 = s + dropout_p1(o Wo^T + bo);  x2 = norm2(s1)
+        y2 = linear2(dropout_pf(relu(linear1(x2))))
+    One launch each way; either direction can stay on the launches it replaces (enc_post_fwd /
+    enc_post_bwd), which produce the same tensors.  The weight, bias and LayerNorm gradients are
+    queued or computed exactly as _RowsLinear, _ResNorm and _FFN do."""
+
+    @staticmethod
+    def forward(ctx, meta, s, o, wo, bo, g2, be2, w1, b1, w2, b2):
+        p1, pf, site1, site_ffn, eps, shape = meta
+        bf = torch.bfloat16
+        C = shape[-1]
+        sr = s.reshape(-1, C).contiguous()
+        orr = o.reshape(-1, C).contiguous()
+        R = sr.shape[0]
+        dev = sr.device
+        woc, w1c, w2c = gemm.cast_param(wo, bf), gemm.cast_param(w1, bf), gemm.cast_param(w2, bf)
+        boc, b1c, b2c = (_al16(gemm.cast_param(b, bf)) for b in (bo, b1, b2))
+        F = w1c.shape[0]
+        kq = int(gemm.ROWS_GEMM and R <= gemm.ROWS_GEMM_MAX_M)
+        seed = flash._seed(dev) if (p1 > 0 or pf > 0) else None
+        s1 = torch.empty((R, C), dtype=torch.float32, device=dev)
+        mean = torch.empty(R, dtype=torch.float32, device=dev)
+        rstd = torch.empty(R, dtype=torch.float32, device=dev)
+        x2 = torch.empty((R, C), dtype=bf, device=dev)
+        if enc_post_fwd:
+            h = torch.empty((R, F), dtype=bf, device=dev)
+            y2 = torch.empty((R, C), dtype=bf, device=dev)
+            _native.call("ov3d_enc_post_fwd", R, sr, orr, woc, woc.stride(0), boc, float(p1), seed,
+                         site1, g2, be2, float(eps), w1c, w1c.stride(0), b1c, float(pf), site_ffn,
+                         w2c, w2c.stride(0), b2c, kq, s1, mean, rstd, x2, h, y2, like=sr)
+        else:
+            y1 = gemm.act_gemm(orr, woc, boc, True)
+            _native.call("ov3d_resnorm_fwd", R, C, sr, 0, y1, 1, float(p1), seed if p1 > 0 else None,
+                         site1, g2, be2, None, 0, None, None, float(eps), s1, mean, rstd, x2, None,
+                         None, 0, 0, 0, 0, like=sr)
+            h = gemm.act_gemm(x2, w1c, b1c, True, 1, pf, seed if pf > 0 else None, site_ffn)
+            y2 = gemm.act_gemm(h, w2c, b2c, True)
+        ctx.save_for_backward(s1, mean, rstd, g2, None, orr, x2, h, woc, w1c, w2c)
+        ctx.seed = seed if p1 > 0 else None
+        ctx.params = (g2, be2, None, None)
+        ctx.lin = (wo, bo, w1, b1, w2, b2)
+        ctx.meta = (p1, site1, R, C, shape, torch.float32, bf, None)
+        ctx.fans = (None, None)
+        ctx.ffn = (float(pf), kq, s.dtype, o.dtype)
+        return s1.view(shape), y2.view(shape)
+
+    @staticmethod
+    def backward(ctx, ds1, dy2):
+        s1, mean, rstd, g2, _, orr, x2, h, woc, w1c, w2c = ctx.saved_tensors
+        wo, bo, w1, b1, w2, b2 = ctx.lin
+        be2 = ctx.params[1]
+        p1, site1, R, C, shape = ctx.meta[:5]
+        pf, kq, sdt, odt = ctx.ffn
+        need = ctx.needs_input_grad   # meta, s, o, wo, bo, g2, be2, w1, b1, w2, b2
+        bf = torch.bfloat16
+        dev = s1.device
+        dy2r = dy2.reshape(R, C).to(bf).contiguous()
+        if not enc_post_bwd:
+            d1 = gemm.act_gemm(dy2r, w2c, None, False, 2, pf, h=h)
+            dw2, db2 = gemm.linear_weight_grads(dy2r, h, w2, b2, need[9], need[10])
+            dw1, db1 = gemm.linear_weight_grads(d1, x2, w1, b1, need[7], need[8])
+            dx2 = gemm.act_gemm(d1, w1c, None, False)
+            ds, dy1, _, dg2, dbe2, _, _ = _bwd_core(
+                ctx, ds1, dx2, None, None, (False, True, True, False, need[5], need[6], False, False))
+            ds, dy1 = ds.reshape(R, C), dy1.reshape(R, C)
+            dout = gemm._dgrad(dy1, woc)
+        else:
+            lib = _native.load()
+            nparts = lib.ov3d_resnorm_bwd_parts(R, C)
+            ds1r = ds1.reshape(R, C).to(torch.float32).contiguous()
+            ds = torch.empty((R, C), dtype=torch.float32, device=dev)
+            dy1 = torch.empty((R, C), dtype=bf, device=dev)
+            dout = torch.empty((R, C), dtype=bf, device=dev)
+            d1 = torch.empty((R, h.shape[1]), dtype=bf, device=dev)
+            partials = torch.empty((nparts, 4, C), dtype=torch.float32, device=dev)
+            _native.call("ov3d_enc_post_bwd", R, ds1r, dy2r, s1, mean, rstd, h, g2, woc,
+                         woc.stride(0), w1c, w1c.stride(0), w2c, w2c.stride(0), float(p1), ctx.seed,
+                         site1, float(pf), kq, ds, dy1, dout, d1, partials, nparts, like=s1)
+            dw2, db2 = gemm.linear_weight_grads(dy2r, h, w2, b2, need[9], need[10])
+            dw1, db1 = gemm.linear_weight_grads(d1, x2, w1, b1, need[7], need[8])
+            dg2 = dbe2 = None
+            slots = [(k, t) for k, t in ((0, g2), (1, be2)) if need[5 + k]]
+            if slots and gemm.DEFER_WGRAD and not torch.is_grad_enabled() and \
+                    gemm._leaf_param(g2) is g2 and gemm._leaf_param(be2) is be2:
+                gemm.defer_norm_grads(partials, nparts, C, slots)
+            elif slots:
+                dg2 = torch.empty(C, dtype=torch.float32, device=dev) if need[5] else None
+                dbe2 = torch.empty(C, dtype=torch.float32, device=dev) if need[6] else None
+                _colsums(partials, nparts, C, (dg2, dbe2, None, None), 0)
+        dwo, dbo = gemm.linear_weight_grads(dy1, orr, wo, bo, need[3], need[4])
+        ds = ds.view(shape).to(sdt) if need[1] else None
+        dout = dout.view(shape).to(odt) if need[2] else None
+        return None, ds, dout, dwo, dbo, dg2, dbe2, dw1, db1, dw2, db2
+
+
+def encoder_post(s, o, wo, bo, norm2, linear1, linear2, p1, pf, sites_):
+    """-> (s1, y2) of _EncPost for the residual stream s and the attention output o (the
+    out-projection wo / bo not yet applied), or None when the fused launches do not apply (the
+    caller then runs resnorm() and ffn()).  sites_ = (site of dropout_p1, site of the FFN's)."""
+    if not (enc_post and enabled and fused_ffn and s is not None and s.is_cuda
+            and s.dtype == torch.float32 and o.dtype == torch.bfloat16 and o.shape == s.shape
+            and torch.is_autocast_enabled("cuda")
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+        return None
+    if bo is None or linear1.bias is None or linear2.bias is None or norm2 is None or \
+            not supported(s, norm2):
+        return None
+    shape = tuple(s.shape)
+    C = shape[-1]
+    R = s.numel() // C
+    F = linear1.weight.shape[0]
+    if tuple(wo.shape) != (C, C) or tuple(linear1.weight.shape) != (F, C) or \
+            tuple(linear2.weight.shape) != (C, F):
+        return None
+    if not _native.load().ov3d_enc_post_supported(R, C, F):
+        return None
+    # the launches this replaces must be the kernels whose arithmetic encpost.hip repeats:
+    # rowsgemm on short row blocks, else tilegemm (not gemm256's rows)
+    if not (gemm.ROWS_GEMM and R <= gemm.ROWS_GEMM_MAX_M) and \
+            not (gemm.TILE_GEMM and gemm.ROWS_GEMM_MAX_M < R < gemm.GEMM256_MIN_M):
+        return None
+    meta = (float(p1), float(pf), int(sites_[0]), int(sites_[1]), norm2.eps, shape)
+    with torch.autocast("cuda", enabled=False):
+        return _EncPost.apply(meta, s, o, wo, bo, norm2.weight, norm2.bias, linear1.weight,
+                              linear1.bias, linear2.weight, linear2.bias)
+
+
 def _ffn_ok(x, linear1, linear2, activation):
     if not isinstance(activation, nn.ReLU):
         return False

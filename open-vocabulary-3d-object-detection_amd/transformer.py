@@ -280,6 +280,13 @@ class TransformerEncoderLayer(nn.Module):
         y = self.self_attn(qk, qk, x, attn_mask=src_mask, defer_out=self.use_ffn)
         if not self.use_ffn:
             return rn.Pending(s, y, p1, site1)
+        if isinstance(y, rn.LinY) and isinstance(self.activation, nn.ReLU):
+            # the whole chain up to linear2 in one launch each way (csrc/encpost.hip)
+            pf = self.dropout.p if self.dropout.training else 0.0
+            r = rn.encoder_post(s, y.x, y.w, y.b, self.norm2, self.linear1, self.linear2, p1, pf,
+                                (site1, site_ffn))
+            if r is not None:
+                return rn.Pending(r[0], r[1], p2, site2)
         s, x, _, _ = rn.resnorm(rn.Pending(s, y, p1, site1), self.norm2)
         y = rn.ffn(x, self.linear1, self.linear2, self.activation, self.dropout, site_ffn)
         return rn.Pending(s, y, p2, site2)

@@ -1069,6 +1069,55 @@ typedef struct {
 } ov3d_sun_labels_args;
 int ov3d_sun_labels(const ov3d_sun_labels_args* args, int pc_f64, void* stream);
 
+/* ---- ScanNet training batches on the device (csrc/scanaug.hip) ----
+ * Replaces ScannetDetectionDataset.__getitem__ (datasets/scannet.py:256-417; use_image and
+ * use_height off).  Raw scans stay resident: raw (S, n_stride, 6) T vertices (xyz + rgb; T float,
+ * or double with pc_f64), boxes (S, k_stride, 7) f64 (centre, lengths, nyu40 id), nverts / nbox
+ * (S) int32.  The host draws the random plan with the reference's numpy calls:
+ *   choices (B, N) int64: np.random.choice of random_sampling (pc_util.py:28), each < nverts
+ *   params  (B, 8) f64: [flip_x, flip_y, cos(rot_angle), sin(rot_angle), 0, 0, 0, 0]
+ * Entry points, in stream order (one launch each, no device -> host read):
+ *   ov3d_scan_sample_aug: out_pc[b, j] = augment(raw[scene_idx[b], choices[b, j]]) as float32
+ *                         (B, N, 3 or 6 with use_color: normalised colour), out_color (B, N, 3) T
+ *                         (raw colour, or the normalised one with use_color) and dims_part
+ *                         (B, ov3d_scan_parts(N), 6) T partial min / max of the written xyz
+ *   ov3d_scan_labels    : every label tensor of the reference's ret_dict (the zero angle arrays
+ *                         included) and point_cloud_dims_min / max
+ *   ov3d_rows_gather    : out[b, j, :] = feat[scene_idx[b], choices[b, j], :] for rows of
+ *                         row_bytes bytes (even); vec_bytes 16 / 4 / 2 picks the access width
+ *                         (0: the widest that row_bytes and both base pointers allow); -1 when
+ *                         the pointers or row_bytes are misaligned for the width asked for. */
+int ov3d_scan_parts(int n);
+int ov3d_scan_sample_aug(const void* raw, int pc_f64, long long n_stride, int S,
+                         const int64_t* scene_idx, const int32_t* nverts, const int64_t* choices,
+                         int B, int N, const double* params, int augment, int use_color,
+                         float* out_pc, void* out_color, void* dims_part, void* stream);
+typedef struct {
+    int B, S, max_num_obj, k_stride, augment, n_dims_part, n_id2class, pc_f64;
+    const double* boxes;      /* (S, k_stride, 7) raw boxes */
+    const int32_t* nbox;      /* (S) */
+    const int64_t* scene_idx; /* (B) */
+    const double* params;     /* (B, 8) */
+    const void* dims_part;    /* (B, n_dims_part, 6) T of ov3d_scan_sample_aug */
+    const int32_t* id2class;  /* (n_id2class) nyu40 id -> class */
+    float* dims_min;          /* (B, 3) point_cloud_dims_min */
+    float* dims_max;          /* (B, 3) */
+    float* corners;           /* (B, G, 8, 3) gt_box_corners */
+    float* centers;           /* (B, G, 3) gt_box_centers */
+    float* centers_normalized;/* (B, G, 3) */
+    int64_t* sem_cls;         /* (B, G) gt_box_sem_cls_label */
+    float* present;           /* (B, G) gt_box_present */
+    float* sizes;             /* (B, G, 3) gt_box_sizes */
+    float* sizes_normalized;  /* (B, G, 3) */
+    float* angles;            /* (B, G) gt_box_angles: zeros */
+    int64_t* angle_cls;       /* (B, G) gt_angle_class_label: zeros */
+    float* angle_res;         /* (B, G) gt_angle_residual_label: zeros */
+} ov3d_scan_labels_args;
+int ov3d_scan_labels(const ov3d_scan_labels_args* args, void* stream);
+int ov3d_rows_gather(const void* feat, long long rows_per_scene, long long row_bytes, int S,
+                     const int64_t* scene_idx, const int64_t* choices, int B, int N,
+                     int vec_bytes, void* out, void* stream);
+
 /* ---- detection evaluation on the device (csrc/evaldet.hip) ----
  * Replaces the CPU evaluation of utils/ap_calculator.py + utils/eval_det.py.
  *   ov3d_box_points_count: remove_empty_box (ap_calculator.py:70-84): for every predicted box

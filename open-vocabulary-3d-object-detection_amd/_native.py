@@ -115,6 +115,9 @@ _SIGS = {
     "ov3d_sun_cuboid_eval": "piipppiiippippppp",
     "ov3d_sun_crop_sample": "piipppiippipppp",
     "ov3d_sun_labels": "pip",
+    "ov3d_scan_sample_aug": "pilipppiipiipppp",
+    "ov3d_scan_labels": "pp",
+    "ov3d_rows_gather": "pllippiiipp",
     "ov3d_box_points_count": "pllipiipp",
     "ov3d_box3d_iou_eval": "ppppiiipp",
     "ov3d_ap_match": "ppppiiiidpp",
@@ -146,7 +149,7 @@ EXPORTS = tuple(_SIGS) + ("ov3d_version", "ov3d_sa_layer_supported", "ov3d_attn_
                           "ov3d_attnpool_fused_supported", "ov3d_lngemm_supported",
                           "ov3d_lngemm_bwd_parts", "ov3d_lngemm_stamps_arm", "ov3d_stream_create",
                           "ov3d_ball_query_ws_bytes", "ov3d_rows256_supported",
-                          "ov3d_enc_post_supported")
+                          "ov3d_enc_post_supported", "ov3d_scan_parts")
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_longlong, "f": ctypes.c_float,
        "d": ctypes.c_double}
@@ -217,6 +220,8 @@ def load():
         lib.ov3d_tile_gemm_supported.restype = ctypes.c_int
         lib.ov3d_sun_range_parts.argtypes = [ctypes.c_int]
         lib.ov3d_sun_range_parts.restype = ctypes.c_int
+        lib.ov3d_scan_parts.argtypes = [ctypes.c_int]
+        lib.ov3d_scan_parts.restype = ctypes.c_int
         lib.ov3d_heads_out_max_text.argtypes = []
         lib.ov3d_heads_out_max_text.restype = ctypes.c_int
         lib.ov3d_attnpool_fused_supported.argtypes = [ctypes.c_int] * 3
@@ -395,6 +400,17 @@ class SunLabelsArgs(ctypes.Structure):
                                                 "centers_normalized", "sem_cls", "present", "sizes",
                                                 "sizes_normalized", "angles", "angle_cls",
                                                 "angle_res")]
+
+
+class ScanLabelsArgs(ctypes.Structure):
+    """ov3d_scan_labels_args (include/ov3d.h)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "S", "max_num_obj", "k_stride", "augment",
+                                             "n_dims_part", "n_id2class", "pc_f64")] + \
+               [(n, ctypes.c_void_p) for n in ("boxes", "nbox", "scene_idx", "params", "dims_part",
+                                                "id2class", "dims_min", "dims_max", "corners",
+                                                "centers", "centers_normalized", "sem_cls",
+                                                "present", "sizes", "sizes_normalized", "angles",
+                                                "angle_cls", "angle_res")]
 
 
 def byref(struct):

@@ -59,9 +59,34 @@ class ScannetDatasetConfig(_Base):
                  "toilet", "sink", "bathtub", "garbagebin"]
         self.type2class = {n: i for i, n in enumerate(names)}
         self.class2type = {v: k for k, v in self.type2class.items()}
+        self.max_num_obj = 64
+        # the 18 detection classes' NYU40 ids, in class order (scannet.py:64-69)
+        self.nyu40ids = np.array([3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39])
+        self.nyu40id2class = {i: c for c, i in enumerate(list(self.nyu40ids))}
 
     def angle2class(self, angle):
         raise ValueError("ScanNet does not have rotated bounding boxes.")
+
+    @staticmethod
+    def rotate_aligned_boxes(input_boxes, rot_mat):
+        """(K, 6) axis-aligned boxes (centre, lengths) rotated about z and re-aligned: the
+        rotated centres, and per box twice the largest x / y of its four rotated half-extent
+        corners (scannet.py:148-169, with the reference's numpy dtype rules); z length kept"""
+        ctr, length = input_boxes[:, 0:3], input_boxes[:, 3:6]
+        rt = np.transpose(rot_mat)
+        new_ctr = np.dot(ctr, rt)
+        hx, hy = length[:, 0] / 2.0, length[:, 1] / 2.0
+        ext_x = np.zeros((hx.shape[0], 4))
+        ext_y = np.zeros((hx.shape[0], 4))
+        for q, (sx, sy) in enumerate(((-1, -1), (1, -1), (1, 1), (-1, 1))):
+            corner = np.zeros((hx.shape[0], 3))
+            corner[:, 0] = sx * hx
+            corner[:, 1] = sy * hy
+            corner = np.dot(corner, rt)
+            ext_x[:, q] = corner[:, 0]
+            ext_y[:, q] = corner[:, 1]
+        new_len = np.stack((2.0 * np.max(ext_x, 1), 2.0 * np.max(ext_y, 1), length[:, 2]), axis=1)
+        return np.concatenate([new_ctr, new_len], axis=1)
 
     def class2anglebatch_tensor(self, pred_cls, residual, to_label_format=True):
         return torch.zeros(pred_cls.shape[:2], dtype=torch.float32, device=pred_cls.device)

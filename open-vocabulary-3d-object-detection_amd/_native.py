@@ -8,155 +8,92 @@ surrounding torch work and capturable into a hipGraph.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libov3d_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ov3d.h")
 
 OV3D_GIOU_CYTHON = 0
 OV3D_GIOU_TENSOR = 1
 
 _lib = None
 
-# name -> argtypes ("p" pointer, "i" int, "l" long long, "f" float, "d" double)
-_SIGS = {
-    "ov3d_fps": "piiipppp",
-    "ov3d_fps_pair_status": "piiipp",
-    "ov3d_ball_query": "ppiiifipp",
-    "ov3d_ball_query_cells": "ppiiifipplp",
-    "ov3d_group_fwd": "ppplllpiiiiifipp",
-    "ov3d_group_bwd": "ppiiiiilllpp",
-    "ov3d_gather_fwd": "ppiiiipp",
-    "ov3d_gather_bwd": "ppiiiipp",
-    "ov3d_giou3d": "pppiiiiipipp",
-    "ov3d_giou3d_bwd_aligned": "pppiiippp",
-    "ov3d_giou3d_bwd": "pppiiiipppp",
-    "ov3d_hungarian": "ppiiipppp",
-    "ov3d_sa_l1_fwd": "ppiippip",
-    "ov3d_sa_l1_fwd_cin": "pipiippip",
-    "ov3d_sa_layer_fwd": "ppppiiipppip",
-    "ov3d_sa_layer_fwd_x0": "pppppiiippip",
-    "ov3d_sa_layer_pool_fwd": "ppppiiiipppppppip",
-    "ov3d_sa_layer_dy": "ppppiiiippppppip",
-    "ov3d_reduce_partials": "piipp",
-    "ov3d_reduce_partials_f32": "piipp",
-    "ov3d_colsum_f32": "piipp",
-    "ov3d_bn_finalize": "pdippffpppppppp",
-    "ov3d_sa_pool_fwd": "ppppppiiipppp",
-    "ov3d_sa_pool_bwd": "ppppppiiippip",
-    "ov3d_bn_bwd_finalize": "pdippppppppp",
-    "ov3d_bn_relu_bwd": "ippppppppppiippipp",
-    "ov3d_bn_relu_bwd_cin": "ippppppppppiiippipp",
-    "ov3d_nms3d": "ppiiidiipp",
-    "ov3d_nms_boxes_from_corners": "pppiipp",
-    "ov3d_clip_preprocess": "plppiiifffffffipp",
-    "ov3d_roi_align_fwd": "piiiiipiiifiiipp",
-    "ov3d_roi_align_pool2_fwd": "piiiiipiiifiiippp",
-    "ov3d_im2col3x3": "piiiiiiipp",
-    "ov3d_bias_residual_act": "pilippip",
-    "ov3d_avgpool2_nhwc": "piiiiipp",
-    "ov3d_attnpool_tokens": "piiiippp",
-    "ov3d_attnpool_mean": "piiippp",
-    "ov3d_attnpool_fused": "pppplliiiipp",
-    "ov3d_attn_fwd": "pppllliiiiffpiplpppip",
-    "ov3d_attn_bwd": "ppplllplplpiiiiffppplplplpip",
-    "ov3d_attn_bwd_dkdv_batch": "piiiiiffp",
-    "ov3d_attn_fwd_masked": "pppllliiiiffpiplpppipp",
-    "ov3d_attn_fwd_pregen": "pppllliiiiffpiplpppipp",
-    "ov3d_attn_dropgen": "iiiifpipp",
-    "ov3d_attn_bwd_masked": "ppplllplplpiiiiffppplplplpipp",
-    "ov3d_attn_mask_pack": "pifiiipp",
-    "ov3d_nbr_max_fwd": "pliippp",
-    "ov3d_set_loss_fwd_split": "ppppppp",
-    "ov3d_group_inverse": "piiiippppp",
-    "ov3d_group_bwd_csr": "pppiiilllpp",
-    "ov3d_group_bwd_csr_bf16": "plppiiilllpp",
-    "ov3d_group_rows_bf16": "ppplllpiiiiifiipp",
-    "ov3d_nbr_max_bwd": "ppliipp",
-    "ov3d_nbr_max_bnrelu_fwd": "pliippppp",
-    "ov3d_rows_bn_bwd_pooled": "ippiplippppppppipp",
-    "ov3d_wgrad": "plpliiiplpppip",
-    "ov3d_wgrad_bn": "plpliiippplpppip",
-    "ov3d_wgrad_group": "pipp",
-    "ov3d_rows_bn_stats": "pillilipip",
-    "ov3d_rows_bn_apply": "pillilippfpipllip",
-    "ov3d_rows_bn_bwd": "ipllipillilipppppppfpipipllip",
-    "ov3d_set_loss_fwd": "pppppp",
-    "ov3d_matcher_cost": "iiiiiiplpppppffffpp",
-    "ov3d_targets_prep": "iiipppppppp",
-    "ov3d_set_loss_bwd": "pppppppppppp",
-    "ov3d_adamw_step": "pppipfpddfpifpp",
-    "ov3d_adamw_set_grads": "pipp",
-    "ov3d_multi_copy": "ipppp",
-    "ov3d_add_cast_bf16": "piplppp",
-    "ov3d_seed_next": "ppp",
-    "ov3d_fourier_pe": "piipppiiipp",
-    "ov3d_box_param_fwd": "liiiiplpppppppppppppppp",
-    "ov3d_box_param_bwd": "liiiplppppppppppppplp",
-    "ov3d_relu_dropout_fwd": "plifpipp",
-    "ov3d_relu_dropout_bwd": "pplfpp",
-    "ov3d_resnorm_fwd": "lipipifpipppippfppppppilllp",
-    "ov3d_resnorm_bwd": "lipppppppilllppfpippipipippppip",
-    "ov3d_rows_gemm": "iiiplplipplp",
-    "ov3d_bn_stats_finalize": "piidppffpppppppp",
-    "ov3d_colsum_group": "pipiip",
-    "ov3d_sa_dy_fused": "ppppiiiipppppppppppip",
-    "ov3d_sa_dy2_fused": "pppppppppppppppiiipppip",
-    "ov3d_bn_bwd_stats_finalize": "piidppppppppp",
-    "ov3d_rows_gemm_act": "iiiplplipifpiplplp",
-    "ov3d_rows_gemm_group": "iipip",
-    "ov3d_tile_gemm": "iiiplplipplp",
-    "ov3d_tile_gemm_act": "iiiplplipifpiplplp",
-    "ov3d_tile_gemm2": "iiiplpliplpliplp",
-    "ov3d_tile_gemm_batched": "iiiipllpllipllp",
-    "ov3d_sun_aug_points": "pilippiipippp",
-    "ov3d_sun_aug_boxes": "plpppiipipippp",
-    "ov3d_sun_cuboid_eval": "piipppiiippippppp",
-    "ov3d_sun_crop_sample": "piipppiippipppp",
-    "ov3d_sun_labels": "pip",
-    "ov3d_scan_sample_aug": "pilipppiipiipppp",
-    "ov3d_scan_labels": "pp",
-    "ov3d_rows_gather": "pllippiiipp",
-    "ov3d_box_points_count": "pllipiipp",
-    "ov3d_box3d_iou_eval": "ppppiiipp",
-    "ov3d_ap_match": "ppppiiiidpp",
-    "ov3d_ap_curve": "plppiplppp",
-    "ov3d_project_box2d": "pppliipppppp",
-    "ov3d_heads_out_fwd": "plippipiippippppppipp",
-    "ov3d_heads_out_bwd": "pppiiiipiippppppplp",
-    "ov3d_gemm256": "plplpiplpliiiip",
-    "ov3d_conv3x3_gemm256": "piiiiplpiplpliip",
-    "ov3d_gemm256_pair": "pplpplppippliiip",
-    "ov3d_gemm256_batched": "pllpllpliplliiiiip",
-    "ov3d_lngemm_fwd": "ipipfpipppippfppppppilllipifpip",
-    "ov3d_rows256": "pliiplpllpp",
-    "ov3d_rows256_bn": "plppplplpllpp",
-    "ov3d_lngemm_bwd": "ipppppppilllppfpipppipipliifplplp",
-    "ov3d_enc_post_fwd": "ippplpfpippfplpfiplpippppppp",
-    "ov3d_enc_post_bwd": "ipppppppplplplfpifipppppip",
-}
-EXPORTS = tuple(_SIGS) + ("ov3d_version", "ov3d_sa_layer_supported", "ov3d_attn_fwd_workspace",
-                          "ov3d_attn_dropbits_words", "ov3d_attn_maskbits_words", "ov3d_fps_workspace", "ov3d_attn_small_bwd", "ov3d_set_loss_fwd_parts",
-                          "ov3d_wgrad_workspace", "ov3d_wgrad_tiles", "ov3d_wgrad_group_tiles",
-                          "ov3d_set_loss_desc_size",
-                          "ov3d_resnorm_supported", "ov3d_resnorm_bwd_parts",
-                          "ov3d_adamw_chunk", "ov3d_wgrad_group_workspace",
-                          "ov3d_rows_gemm_supported", "ov3d_sa_dy_fused_supported",
-                          "ov3d_tile_gemm_supported", "ov3d_sun_range_parts", "ov3d_heads_out_max_text",
-                          "ov3d_heads_out_workspace", "ov3d_stamps_arm", "ov3d_stamps_count",
-                          "ov3d_stamps_get", "ov3d_wall_clock_khz",
-                          "ov3d_attnpool_fused_supported", "ov3d_lngemm_supported",
-                          "ov3d_lngemm_bwd_parts", "ov3d_lngemm_stamps_arm", "ov3d_stream_create",
-                          "ov3d_ball_query_ws_bytes", "ov3d_rows256_supported",
-                          "ov3d_enc_post_supported", "ov3d_scan_parts")
-
-_CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_longlong, "f": ctypes.c_float,
-       "d": ctypes.c_double}
-
 
 class NativeError(RuntimeError):
     pass
+
+
+# The closed set of C types include/ov3d.h uses.  Any pointer is a c_void_p, so that
+# data_ptr() ints, None and byref() all pass.
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+_RETURNS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "const char *": ctypes.c_char_p}
+
+
+def _ctype(ctype, decl):
+    if "*" in ctype:
+        return ctypes.c_void_p
+    if ctype.strip() not in _SCALARS:
+        raise NativeError(f"include/ov3d.h: `{decl}` has a type the binding does not know "
+                          f"({', '.join(_SCALARS)} or a pointer)")
+    return _SCALARS[ctype.strip()]
+
+
+def read_header(text):
+    """C header text -> ({struct: [(field, ctype)]}, {function: (restype, [argtypes])}) for every
+    `typedef struct { ... } name;` and every prototype; a declaration outside the closed set of
+    types raises NativeError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = dict(re.findall(r"^#define\s+(\w+)\s+\(?(-?\d+)\)?\s*$", text, flags=re.M))
+    text = re.sub(r'^\s*#.*$|extern\s+"C"\s*\{|^\}\s*$', "", text, flags=re.M)
+    structs = {}
+
+    def read_struct(m):
+        fields = structs[m.group(2)] = []
+        for decl in filter(None, (" ".join(d.split()) for d in m.group(1).split(";"))):
+            # type, then one or more names, each with an optional [length]
+            dm = re.fullmatch(r"(.*?[\s*])(\w+(?:\[\w+\])?(?:, ?\w+(?:\[\w+\])?)*)", decl)
+            names = re.findall(r"(\w+)(?:\[(\w+)\])?", dm.group(2)) if dm else []
+            lengths = [defines.get(length, length) for _, length in names]
+            if dm is None or not all(n == "" or n.isdigit() for n in lengths):
+                raise NativeError(f"include/ov3d.h: cannot read the field `{decl}` of {m.group(2)}")
+            ct = _ctype(dm.group(1), decl)
+            fields += [(name, ct * int(n) if n else ct) for (name, _), n in zip(names, lengths)]
+        return ""
+
+    text = re.sub(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", read_struct, text, flags=re.S)
+    protos = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.*?[\s*])(\w+) ?\((.*)\)", decl)
+        ret = m and " ".join(m.group(1).replace("*", " * ").split())
+        if m is None or ret not in _RETURNS:
+            raise NativeError(f"include/ov3d.h: cannot read the declaration `{decl}`")
+        params = [] if m.group(3).strip() == "void" else [p.strip() for p in m.group(3).split(",")]
+        protos[m.group(2)] = (_RETURNS[ret], [_ctype(p if "*" in p else p.rpartition(" ")[0], decl)
+                                              for p in params])
+    return structs, protos
+
+
+def _read_own_header():
+    if not os.path.exists(HEADER_PATH):
+        raise NativeError(f"{HEADER_PATH} not found: the ctypes binding is derived from it")
+    with open(HEADER_PATH) as f:
+        return read_header(f.read())
+
+
+_STRUCT_FIELDS, _PROTOS = _read_own_header()
+EXPORTS = tuple(_PROTOS)
+_STRUCTS = {}
+
+
+def struct(name):
+    """the ctypes.Structure of a struct of include/ov3d.h (fields in the header's order)"""
+    if name not in _STRUCTS:
+        _STRUCTS[name] = type(name, (ctypes.Structure,), {"_fields_": _STRUCT_FIELDS[name]})
+    return _STRUCTS[name]
 
 
 def load():
@@ -168,80 +105,10 @@ def load():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU fallback); "
                 "build it with `make -C open-vocabulary-3d-object-detection_amd/csrc`")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in _SIGS.items():
+        for name, (restype, argtypes) in _PROTOS.items():
             fn = getattr(lib, name)
-            fn.argtypes = [_CT[c] for c in sig]
-            fn.restype = ctypes.c_int
-        lib.ov3d_sa_layer_supported.argtypes = [ctypes.c_int, ctypes.c_int]
-        lib.ov3d_sa_layer_supported.restype = ctypes.c_int
-        lib.ov3d_attn_fwd_workspace.argtypes = [ctypes.c_int] * 5
-        lib.ov3d_attn_fwd_workspace.restype = ctypes.c_longlong
-        lib.ov3d_attn_dropbits_words.argtypes = [ctypes.c_int] * 4
-        lib.ov3d_attn_dropbits_words.restype = ctypes.c_longlong
-        lib.ov3d_set_loss_fwd_parts.argtypes = [ctypes.c_int] * 3
-        lib.ov3d_set_loss_fwd_parts.restype = ctypes.c_longlong
-        lib.ov3d_fps_workspace.argtypes = [ctypes.c_int] * 2
-        lib.ov3d_fps_workspace.restype = ctypes.c_longlong
-        lib.ov3d_stamps_arm.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong]
-        lib.ov3d_stamps_arm.restype = ctypes.c_int
-        lib.ov3d_stamps_count.argtypes = []
-        lib.ov3d_stamps_count.restype = ctypes.c_int
-        lib.ov3d_stamps_get.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4
-        lib.ov3d_stamps_get.restype = ctypes.c_int
-        lib.ov3d_wall_clock_khz.argtypes = []
-        lib.ov3d_wall_clock_khz.restype = ctypes.c_longlong
-        lib.ov3d_attn_small_bwd.argtypes = [ctypes.c_int]
-        lib.ov3d_attn_small_bwd.restype = ctypes.c_int
-        lib.ov3d_attn_maskbits_words.argtypes = [ctypes.c_int] * 3
-        lib.ov3d_attn_maskbits_words.restype = ctypes.c_longlong
-        lib.ov3d_wgrad_workspace.argtypes = [ctypes.c_int] * 4
-        lib.ov3d_wgrad_workspace.restype = ctypes.c_longlong
-        lib.ov3d_wgrad_tiles.argtypes = [ctypes.c_int] * 2
-        lib.ov3d_wgrad_tiles.restype = ctypes.c_int
-        lib.ov3d_wgrad_group_tiles.argtypes = [ctypes.c_int] * 2
-        lib.ov3d_wgrad_group_tiles.restype = ctypes.c_int
-        lib.ov3d_set_loss_desc_size.argtypes = []
-        lib.ov3d_set_loss_desc_size.restype = ctypes.c_longlong
-        lib.ov3d_resnorm_supported.argtypes = [ctypes.c_int]
-        lib.ov3d_resnorm_supported.restype = ctypes.c_int
-        lib.ov3d_resnorm_bwd_parts.argtypes = [ctypes.c_longlong, ctypes.c_int]
-        lib.ov3d_resnorm_bwd_parts.restype = ctypes.c_int
-        lib.ov3d_adamw_chunk.argtypes = []
-        lib.ov3d_adamw_chunk.restype = ctypes.c_int
-        lib.ov3d_wgrad_group_workspace.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        lib.ov3d_wgrad_group_workspace.restype = ctypes.c_longlong
-        lib.ov3d_sa_dy_fused_supported.argtypes = [ctypes.c_int] * 2
-        lib.ov3d_sa_dy_fused_supported.restype = ctypes.c_int
-        lib.ov3d_rows_gemm_supported.argtypes = [ctypes.c_int] * 3
-        lib.ov3d_rows256_supported.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
-        lib.ov3d_rows256_supported.restype = ctypes.c_int
-        lib.ov3d_rows_gemm_supported.restype = ctypes.c_int
-        lib.ov3d_tile_gemm_supported.argtypes = [ctypes.c_int] * 3
-        lib.ov3d_tile_gemm_supported.restype = ctypes.c_int
-        lib.ov3d_sun_range_parts.argtypes = [ctypes.c_int]
-        lib.ov3d_sun_range_parts.restype = ctypes.c_int
-        lib.ov3d_scan_parts.argtypes = [ctypes.c_int]
-        lib.ov3d_scan_parts.restype = ctypes.c_int
-        lib.ov3d_heads_out_max_text.argtypes = []
-        lib.ov3d_heads_out_max_text.restype = ctypes.c_int
-        lib.ov3d_attnpool_fused_supported.argtypes = [ctypes.c_int] * 3
-        lib.ov3d_attnpool_fused_supported.restype = ctypes.c_int
-        lib.ov3d_lngemm_supported.argtypes = [ctypes.c_int] * 3
-        lib.ov3d_lngemm_supported.restype = ctypes.c_int
-        lib.ov3d_lngemm_bwd_parts.argtypes = [ctypes.c_int]
-        lib.ov3d_lngemm_bwd_parts.restype = ctypes.c_int
-        lib.ov3d_lngemm_stamps_arm.argtypes = [ctypes.c_void_p]
-        lib.ov3d_lngemm_stamps_arm.restype = ctypes.c_int
-        lib.ov3d_enc_post_supported.argtypes = [ctypes.c_int] * 3
-        lib.ov3d_enc_post_supported.restype = ctypes.c_int
-        lib.ov3d_heads_out_workspace.argtypes = [ctypes.c_int] * 2
-        lib.ov3d_heads_out_workspace.restype = ctypes.c_longlong
-        lib.ov3d_stream_create.argtypes = [ctypes.c_void_p]
-        lib.ov3d_ball_query_ws_bytes.argtypes = [ctypes.c_int] * 2
-        lib.ov3d_ball_query_ws_bytes.restype = ctypes.c_longlong
-        lib.ov3d_stream_create.restype = ctypes.c_int
-        lib.ov3d_version.argtypes = []
-        lib.ov3d_version.restype = ctypes.c_char_p
+            fn.argtypes = argtypes
+            fn.restype = restype
         _lib = lib
     return _lib
 
@@ -279,10 +146,7 @@ def check_device(t, name):
 
 
 def check(t, name, dtype=None, ndim=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a tensor")
-    if t.device.type != "cuda":
-        raise NativeError(f"{name}: ov3d kernels run on the ROCm device only (got {t.device})")
+    check_device(t, name)
     if dtype is not None and t.dtype != dtype:
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
     if ndim is not None and t.dim() != ndim:
@@ -391,30 +255,12 @@ def call(name, *args, like):
         raise NativeError(f"{name} failed with status {rc}")
 
 
-class SunLabelsArgs(ctypes.Structure):
-    """ov3d_sun_labels_args (include/ov3d.h)"""
-    _fields_ = [(n, ctypes.c_int) for n in ("B", "max_num_obj", "k_max", "num_angle_bin",
-                                             "num_attempts", "n_dims_part")] + \
-               [(n, ctypes.c_void_p) for n in ("boxes", "nbox", "sel", "crop_mm", "dims_part",
-                                                "dims_min", "dims_max", "corners", "centers",
-                                                "centers_normalized", "sem_cls", "present", "sizes",
-                                                "sizes_normalized", "angles", "angle_cls",
-                                                "angle_res")]
-
-
-class ScanLabelsArgs(ctypes.Structure):
-    """ov3d_scan_labels_args (include/ov3d.h)"""
-    _fields_ = [(n, ctypes.c_int) for n in ("B", "S", "max_num_obj", "k_stride", "augment",
-                                             "n_dims_part", "n_id2class", "pc_f64")] + \
-               [(n, ctypes.c_void_p) for n in ("boxes", "nbox", "scene_idx", "params", "dims_part",
-                                                "id2class", "dims_min", "dims_max", "corners",
-                                                "centers", "centers_normalized", "sem_cls",
-                                                "present", "sizes", "sizes_normalized", "angles",
-                                                "angle_cls", "angle_res")]
+SunLabelsArgs = struct("ov3d_sun_labels_args")
+ScanLabelsArgs = struct("ov3d_scan_labels_args")
 
 
 def byref(struct):
-    """address of a ctypes structure, for a "p" argument (the caller keeps it alive)"""
+    """address of a ctypes structure, for a pointer argument (the caller keeps it alive)"""
     return ctypes.c_void_p(ctypes.addressof(struct))
 
 

@@ -47,13 +47,7 @@ _KV_JOBS = {}   # id(dK buffer) -> [((B, H, Lq, Lk, p), job struct, tensors kept
 DEFER_KV = True   # off: every call computes its dK / dV at once (tests compare the two)
 
 
-class _DkdvJob(ctypes.Structure):
-    """mirror of ov3d_attn_dkdv_job (include/ov3d.h)"""
-    _fields_ = [("q", ctypes.c_void_p), ("sq", ctypes.c_longlong), ("k", ctypes.c_void_p),
-                ("sk", ctypes.c_longlong), ("v", ctypes.c_void_p), ("sv", ctypes.c_longlong),
-                ("dout", ctypes.c_void_p), ("sdo", ctypes.c_longlong), ("lse", ctypes.c_void_p),
-                ("dvec", ctypes.c_void_p), ("dropbits", ctypes.c_void_p), ("dk", ctypes.c_void_p),
-                ("sdk", ctypes.c_longlong), ("dv", ctypes.c_void_p), ("sdv", ctypes.c_longlong)]
+_DkdvJob = _native.struct("ov3d_attn_dkdv_job")
 
 
 def defer_kv_grads(dk_buf):

@@ -15,6 +15,8 @@ import weakref
 import torch
 from torch.autograd import Function
 
+from . import _native
+
 _TARGET_TILES = 512     # aim for this many (chunk x 64x64 tile) work items
 _MIN_ROWS = 256         # never split below this many rows per chunk
 
@@ -46,14 +48,12 @@ def _rows_gemm_ok(a, w, trans_b):
         return False
     if a.data_ptr() % 16 or w.data_ptr() % 16 or a.stride(0) % 8 or w.stride(0) % 8:
         return False
-    from . import _native
     return bool(_native.load().ov3d_rows_gemm_supported(M, N, K))
 
 
 def rows_gemm(a, w, bias=None, trans_b=True):
     """a (M, K) bf16 rows; w bf16 (N, K) when trans_b (y = a w^T + bias, nn.Linear) else
     (K, N) (y = a w) -> (M, N) bf16 (csrc/rowsgemm.hip; check _rows_gemm_ok first)"""
-    from . import _native
     M, K = a.shape
     N = w.shape[0] if trans_b else w.shape[1]
     out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
@@ -64,24 +64,13 @@ def rows_gemm(a, w, bias=None, trans_b=True):
     return out
 
 
-class _RgProblem(ctypes.Structure):
-    """mirror of ov3d_rows_gemm_problem (include/ov3d.h)"""
-    _fields_ = [("A", ctypes.c_void_p), ("lda", ctypes.c_longlong), ("W", ctypes.c_void_p),
-                ("ldw", ctypes.c_longlong), ("bias", ctypes.c_void_p), ("C", ctypes.c_void_p),
-                ("ldc", ctypes.c_longlong), ("N", ctypes.c_int), ("K", ctypes.c_int)]
-
-
-class _LnProblem(ctypes.Structure):
-    """mirror of ov3d_lngemm_problem (include/ov3d.h)"""
-    _fields_ = [("W", ctypes.c_void_p), ("ldw", ctypes.c_longlong), ("bias", ctypes.c_void_p),
-                ("out", ctypes.c_void_p), ("ldo", ctypes.c_longlong), ("N", ctypes.c_int),
-                ("sel", ctypes.c_int)]
+_RgProblem = _native.struct("ov3d_rows_gemm_problem")
+_LnProblem = _native.struct("ov3d_lngemm_problem")
 
 
 def rows_gemm_group(problems, trans_b=True):
     """[(a, w, bias)] over the same rows -> [outputs], one launch (every pair must pass
     _rows_gemm_ok; at most 4)"""
-    from . import _native
     M = problems[0][0].shape[0]
     outs, keep, probs = [], [], []
     for a, w, b in problems:
@@ -124,14 +113,12 @@ def _tile_gemm_ok(a, w, trans_b):
         return False
     if a.data_ptr() % 16 or w.data_ptr() % 16 or a.stride(0) % 8 or w.stride(0) % 8:
         return False
-    from . import _native
     return bool(_native.load().ov3d_tile_gemm_supported(M, N, K))
 
 
 def tile_gemm(a, w, bias=None, trans_b=True, out=None):
     """as rows_gemm, on the long row-block kernel (check _tile_gemm_ok first); `out` an (M, N)
     bf16 row view (stride(1) == 1, 16-byte aligned, row stride % 8 == 0) or None"""
-    from . import _native
     M, K = a.shape
     N = w.shape[0] if trans_b else w.shape[1]
     if out is None:
@@ -164,13 +151,11 @@ def tile_bmm_ok(a, w, trans_b):
         return False
     if (a.data_ptr() % 16 or w.data_ptr() % 16 or any(x % 8 for x in a.stride()[:2] + w.stride()[:2])):
         return False
-    from . import _native
     return bool(_native.load().ov3d_tile_gemm_supported(M, N, K))
 
 
 def tile_bmm(a, w, trans_b):
     """torch.bmm(a, w.transpose(1, 2) if trans_b else w) -> (B, M, N) bf16, one launch"""
-    from . import _native
     B, M, K = a.shape
     N = w.shape[1] if trans_b else w.shape[2]
     out = torch.empty((B, M, N), dtype=torch.bfloat16, device=a.device)
@@ -187,7 +172,6 @@ def _aligned_bias(b):
 
 def shape_ok(M, N, K):
     """a (M, K) x (K, N) product on fresh contiguous bf16 rows runs on rows_gemm or tile_gemm"""
-    from . import _native
     lib = _native.load()
     if ROWS_GEMM and M <= ROWS_GEMM_MAX_M:
         return bool(lib.ov3d_rows_gemm_supported(M, N, K))
@@ -203,7 +187,6 @@ def act_gemm(a, w, bias=None, trans_b=True, epilogue=0, p=0.0, seed=None, site=0
     """(M, N) bf16 = a (M, K) x w (w (N, K) when trans_b, else (K, N)) + bias, with the FFN
     epilogue (0 none, 1 dropout_p(relu(.)), 2 h > 0 ? . / (1 - p) : 0) on the short row-block
     kernel (M <= ROWS_GEMM_MAX_M) or the long one; check act_gemm_ok first"""
-    from . import _native
     M, K = a.shape
     N = w.shape[0] if trans_b else w.shape[1]
     out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
@@ -217,7 +200,6 @@ def act_gemm(a, w, bias=None, trans_b=True, epilogue=0, p=0.0, seed=None, site=0
 def tile_gemm2(a1, w1, a2, w2):
     """a1 w1 + a2 w2 (input-gradient layout: w (K, N)) in one launch of the long row-block
     kernel (check _tile_gemm_ok on both pairs first)"""
-    from . import _native
     M, N = a1.shape[0], w1.shape[1]
     out = torch.empty((M, N), dtype=torch.bfloat16, device=a1.device)
     _native.call("ov3d_tile_gemm2", M, N, a1.shape[1], a1, a1.stride(0), w1, w1.stride(0),
@@ -264,7 +246,6 @@ def _bias_arg(bias):
 def gemm256(a, w, bias=None, residual=None, relu=False, out=None):
     """act(a w^T + bias + residual) -> (M, N) bf16 on the 256 x 256 tile kernel (check
     gemm256_ok first); bias bf16 or fp32 (N,), residual (M, N) bf16 rows"""
-    from . import _native
     M, K = a.shape
     N = w.shape[0]
     if out is None:
@@ -279,7 +260,6 @@ def gemm256(a, w, bias=None, residual=None, relu=False, out=None):
 def gemm256_pair(a1, w1, b1, a2, w2, b2):
     """(a1 w1^T + b1, a2 w2^T + b2) in ONE launch of the tile kernel (same shapes; check
     gemm256_ok on both pairs and that a1 / a2, w1 / w2 share their row strides first)"""
-    from . import _native
     M, K = a1.shape
     N = w1.shape[0]
     o1 = torch.empty((M, N), dtype=torch.bfloat16, device=a1.device)
@@ -296,7 +276,6 @@ def gemm256_batched(A, lda, sA, B, ldb, sB, C, ldc, sC, M, N, K, nbatch, bias=No
     rows, K contiguous), bias + p sbias (bf16 or f32, or None) and writes C + p sC (bf16); all
     offsets and leading dimensions in elements of the given base tensors (no shape checks here:
     the C entry validates strides and alignment)"""
-    from . import _native
     bf32 = 0
     if bias is not None:
         bf32 = int(bias.dtype == torch.float32)
@@ -318,7 +297,6 @@ def conv3x3_gemm256(x, w, bias=None, residual=None, relu=False):
     """3x3 convolution (pad 1, stride 1) of NHWC x with the (Cout, 3, 3, C) channels-last weight
     viewed as (Cout, 9C) rows, + bias (+ residual rows) (+ ReLU) -> (n, H, W, Cout) bf16, as an
     implicit GEMM (check conv3x3_ok first)"""
-    from . import _native
     n, H, W, C = x.shape
     cout = w.shape[0]
     out = torch.empty((n, H, W, cout), dtype=torch.bfloat16, device=x.device)
@@ -343,7 +321,6 @@ ROWS256 = os.environ.get("OV3D_ROWS256", "1") != "0"
 def rows256_ok(a, w, bias=None):
     """a (M, K) x w (N, K)^T runs on rows256: (K, N) = (256, 256), (264, 256) (the zero-padded
     first layer) or (256, 264) (its input gradient)"""
-    from . import _native
     K = a.shape[1] if a.dim() == 2 else 0
     N = w.shape[0] if w.dim() == 2 else 0
     return (ROWS256 and bias is None and a.shape[0] >= GEMM256_MIN_M and _rows_ok(a) and _rows_ok(w)
@@ -353,7 +330,6 @@ def rows256_ok(a, w, bias=None):
 
 def rows256(a, w):
     """a (M, K) w (N, K)^T -> (M, N) bf16 (check rows256_ok first)"""
-    from . import _native
     N = w.shape[0]
     out = torch.empty((a.shape[0], N), dtype=torch.bfloat16, device=a.device)
     _native.call("ov3d_rows256", a, a.stride(0), a.shape[1], N, w, w.stride(0), out, out.stride(0),
@@ -449,7 +425,6 @@ def _wg_counters(device):
 
 
 def _wg_splits(R, N, K):
-    from . import _native
     tiles = _native.load().ov3d_wgrad_tiles(N, K)
     # short R: parallelism; long R: fewer partials to sum (tools/wgrad_split_probe.py sweep)
     rows = 128 if R <= 2048 else (256 if R <= 4096 else 512)
@@ -474,7 +449,6 @@ def fused_weight_grad(dy, x, bias=True, out_w=None, out_b=None, bn=None):
     (csrc/wgrad.hip, ov3d_wgrad); dy (R, N), x (R, K) bf16 rows (row strides taken from the
     tensors).  out_w / out_b: optional fp32 destinations (row slices of a larger gradient).
     bn=(scale, shift): x is relu(x * scale + shift) in bf16, applied on load (ov3d_wgrad_bn)."""
-    from . import _native
     R, N = dy.shape
     K = x.shape[1]
     if dy.stride(1) != 1 or x.stride(1) != 1:
@@ -521,14 +495,8 @@ def _ensure_flush():
         _QUEUED[0] = True
 
 
-class _ColSeg(ctypes.Structure):
-    """mirror of ov3d_colsum_seg"""
-    _fields_ = [("partials", ctypes.c_void_p), ("nparts", ctypes.c_int), ("k", ctypes.c_int)]
-
-
-class _ColOut(ctypes.Structure):
-    """mirror of ov3d_colsum_out"""
-    _fields_ = [("dst", ctypes.c_void_p), ("first_seg", ctypes.c_int), ("nseg", ctypes.c_int)]
+_ColSeg = _native.struct("ov3d_colsum_seg")
+_ColOut = _native.struct("ov3d_colsum_out")
 
 
 def defer_norm_grads(partials, nparts, C, slots):
@@ -540,7 +508,6 @@ def defer_norm_grads(partials, nparts, C, slots):
 
 
 def _flush_norm_grads():
-    from . import _native
     cols = list(_PENDING_COLS)
     _PENDING_COLS.clear()
     if not cols:
@@ -571,12 +538,7 @@ def _flush_norm_grads():
                     p.grad.add_(g)
 
 
-class _WgProblem(ctypes.Structure):
-    """mirror of ov3d_wgrad_problem (include/ov3d.h)"""
-    _fields_ = [("dy", ctypes.c_void_p), ("ldy", ctypes.c_longlong), ("x", ctypes.c_void_p),
-                ("ldx", ctypes.c_longlong), ("R", ctypes.c_int), ("N", ctypes.c_int),
-                ("K", ctypes.c_int), ("nsplit", ctypes.c_int), ("dW", ctypes.c_void_p),
-                ("ldw", ctypes.c_longlong), ("db", ctypes.c_void_p)]
+_WgProblem = _native.struct("ov3d_wgrad_problem")
 
 
 def _leaf_param(w):
@@ -610,7 +572,6 @@ def defer_weight_grad(dy, x, w, b=None, rows=None, bn=None):
 
 def flush_weight_grads():
     """run every queued weight gradient in one grouped launch and store them as .grad"""
-    from . import _native
     _QUEUED[0] = False
     _flush_norm_grads()
     items = list(_PENDING)

@@ -33,12 +33,7 @@ from . import _native
 from . import gemm
 
 
-class _Entry(ctypes.Structure):
-    """mirror of ov3d_adamw_tensor (include/ov3d.h)"""
-    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p),
-                ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
-                ("shadow", ctypes.c_void_p), ("numel", ctypes.c_longlong),
-                ("group", ctypes.c_int), ("reserved", ctypes.c_int)]
+_Entry = _native.struct("ov3d_adamw_tensor")
 
 
 class FusedAdamW(torch.optim.Optimizer):

@@ -25,6 +25,7 @@ from torch import nn
 from . import _native
 from . import attention as flash
 from . import gemm
+from .gemm import _ColOut, _ColSeg, _LnProblem
 
 Pending = namedtuple("Pending", "src y p site")
 # a branch output not yet computed: y = x w^T + b (the sub-layer's output projection / FFN
@@ -258,7 +259,6 @@ def _colsums(partials, nparts, C, outs, acc):
     """LayerNorm parameter gradients (dga, dba, dgb, dbb) from (nparts, 4, C) partials in
     one ov3d_colsum_group launch (the fixed summation order of resnorm_bwd's own column
     pass); acc bits 2 / 4: add into dga / dba, dgb / dbb (gradient fan-in)."""
-    from .gemm import _ColSeg, _ColOut
     import ctypes
     tmp = torch.empty((4, C), dtype=torch.float32, device=partials.device)
     segs = (_ColSeg * 4)(*[_ColSeg(partials.data_ptr(), nparts, k) for k in range(4)])
@@ -357,7 +357,6 @@ class _LnGemm(torch.autograd.Function):
             xb = torch.empty((R, C), dtype=torch.float32, device=dev) if want_b else None
         gwc, gbc = gemm.cast_param(gw, bf), gemm.cast_param(gbias, bf)
         outs, probs = [], []
-        from .gemm import _LnProblem
         import ctypes
         for sel, r0, r1 in spec:
             o = torch.empty((R, r1 - r0), dtype=bf, device=dev)

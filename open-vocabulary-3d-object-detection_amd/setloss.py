@@ -24,24 +24,7 @@ COLUMNS = ("loss_sem_cls", "loss_angle_cls", "loss_angle_reg", "loss_center", "l
            "loss_giou", "loss_2dalignment", "loss_cardinality")
 SEM, CENTER, SIZE, GIOU, ALIGN = 1, 2, 4, 8, 16
 MAX_B = 256
-_P = ctypes.c_void_p
-_L = ctypes.c_longlong
-
-
-class Desc(ctypes.Structure):
-    """mirror of ov3d_set_loss_desc (include/ov3d.h)"""
-    _fields_ = [("L", ctypes.c_int), ("B", ctypes.c_int), ("Q", ctypes.c_int), ("G", ctypes.c_int),
-                ("T", ctypes.c_int), ("NB", ctypes.c_int), ("flags", ctypes.c_int),
-                ("final_last", ctypes.c_int), ("match_ref_order", ctypes.c_int),
-                ("logits", _P), ("ld_logits", _L), ("angle_logits", _P), ("ld_angle_logits", _L),
-                ("angle_res", _P), ("ld_angle_res", _L), ("center", _P), ("ld_center", _L),
-                ("size", _P), ("ld_size", _L), ("gious", _P), ("inds", _P), ("matched", _P),
-                ("gt_sem", _P), ("gt_angle_cls", _P), ("gt_angle_res", _P), ("gt_center", _P),
-                ("gt_size", _P), ("nactual", _P), ("cls_weights", _P), ("num_boxes", _P),
-                ("align", _P), ("dict_w", ctypes.c_float * 8), ("total_w", ctypes.c_float * 8),
-                ("total_order", ctypes.c_int * 8), ("n_total", ctypes.c_int),
-                ("res_scale", ctypes.c_float), ("match_status", _P), ("n_status", ctypes.c_int)]
-
+Desc = _native.struct("ov3d_set_loss_desc")
 
 _checked = False
 _tickets = {}

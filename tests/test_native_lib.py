@@ -3,6 +3,8 @@ and the product refuses CPU tensors (no silent fallback).  No compute here."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -25,25 +27,114 @@ def test_library_exports_every_header_symbol():
     assert set(syms) == set(_native.EXPORTS)
 
 
-def test_ctypes_signatures_match_header_arity():
-    """_native._SIGS (argument kinds incl. the trailing stream) vs the header prototypes."""
+P, I, L, F, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double
+# written out from the prototypes of include/ov3d.h: name -> (restype, argtypes)
+EXPECTED = {
+    "ov3d_version": (ctypes.c_char_p, []),
+    "ov3d_wall_clock_khz": (L, []),
+    "ov3d_fps": (I, [P, I, I, I, P, P, P, P]),
+    "ov3d_bn_finalize": (I, [P, D, I, P, P, F, F, P, P, P, P, P, P, P, P]),
+    "ov3d_nms3d": (I, [P, P, I, I, I, D, I, I, P, P]),
+    "ov3d_multi_copy": (I, [I, P, P, P, P]),
+    "ov3d_stream_create": (I, [P]),
+    "ov3d_stamps_arm": (I, [P, L, L]),
+    "ov3d_stamps_get": (I, [I, P, P, P, P]),
+    "ov3d_wgrad_group_workspace": (L, [P, I]),
+    "ov3d_resnorm_bwd_parts": (I, [L, I]),
+    "ov3d_scan_labels": (I, [P, P]),
+    "ov3d_attn_bwd_dkdv_batch": (I, [P, I, I, I, I, I, F, F, P]),
+}
+
+
+def test_derived_signatures_match_written_out_expectations():
+    """argtypes / restype that _native derives from the header vs literals written from it by hand"""
     from ov3d_amd import _native
+    lib = _native.load()
+    for name, (restype, argtypes) in EXPECTED.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == argtypes, name
+
+
+def test_every_header_symbol_is_bound():
+    """every prototype this test's own regular expression finds resolves in the library and has
+    argtypes of its parameter count; nothing is left to ctypes' int default"""
+    from ov3d_amd import _native
+    lib = _native.load()
     src = open(os.path.join(ROOT, "include", "ov3d.h")).read()
-    protos = dict(re.findall(r"^int\s+(ov3d_\w+)\(([^)]*)\);", src, flags=re.M))
-    for name, sig in _native._SIGS.items():
-        params = [a.strip() for a in protos[name].split(",")]
-        assert len(params) == len(sig), (name, len(params), len(sig))
-        for a, k in zip(params, sig):
-            if "*" in a:
-                assert k == "p", (name, a)
-            elif a.startswith("double"):
-                assert k == "d", (name, a)
-            elif a.startswith("float"):
-                assert k == "f", (name, a)
-            elif a.startswith("long long"):
-                assert k == "l", (name, a)
-            else:
-                assert k == "i", (name, a)
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = dict(re.findall(r"^(?:int|long long|const char\*)\s+(ov3d_\w+)\(([^)]*)\);", src, flags=re.M))
+    assert sorted(protos) == header_symbols()
+    assert set(protos) == set(_native.EXPORTS) and len(_native.EXPORTS) == len(protos)
+    for name, params in protos.items():
+        n = 0 if params.strip() == "void" else len(params.split(","))
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == n, (name, n)
+        assert fn.restype in (ctypes.c_int, ctypes.c_longlong, ctypes.c_char_p), name
+
+
+def test_struct_layouts_match_the_c_compiler(tmp_path):
+    """sizeof and every offsetof of each struct of the header, as the host C compiler lays it
+    out, vs the ctypes.Structure _native derives"""
+    from ov3d_amd import _native
+    cc = shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler (cc) on PATH")
+    src = open(os.path.join(ROOT, "include", "ov3d.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    structs = re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S)
+    assert len(structs) >= 10
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ov3d.h"', "int main(void) {"]
+    for body, name in structs:
+        cls = _native.struct(name)
+        assert cls is _native.struct(name)           # cached
+        # the field names, by this test's own reading: the last word of each declarator
+        fields = [re.sub(r"\[.*", "", d).split()[-1].lstrip("*") for decl in body.split(";")
+                  if decl.strip() for d in decl.split(",")]
+        assert [f for f, _ in cls._fields_] == fields, name
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"),
+                    str(tmp_path / "layout.c")], check=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    seen = 0
+    for key, value in (ln.split() for ln in out.splitlines()):
+        name, _, field = key.partition(".")
+        cls = _native.struct(name)
+        got = getattr(cls, field).offset if field else ctypes.sizeof(cls)
+        assert got == int(value), (key, got, value)
+        seen += 1
+    assert seen == sum(1 + len(_native.struct(n)._fields_) for _, n in structs)
+    desc = _native.struct("ov3d_set_loss_desc")
+    assert desc.dict_w.size == 8 * 4 and desc.total_order.size == 8 * 4   # arrays sized by a #define
+
+
+def test_reader_rejects_types_outside_the_closed_set():
+    """nothing defaults to int: an unknown parameter, field or return type raises, naming the
+    declaration"""
+    from ov3d_amd import _native
+    good = ("typedef struct { int a, b; float w[2]; const void* p; } ov3d_t;\n"
+            "int ov3d_f(const ov3d_t* t, double x);\n")
+    structs, protos = _native.read_header(good)
+    assert structs == {"ov3d_t": [("a", I), ("b", I), ("w", F * 2), ("p", P)]}
+    assert protos == {"ov3d_f": (I, [P, D])}
+    with pytest.raises(_native.NativeError, match=r"ov3d_g\(int n, short k\)"):
+        _native.read_header(good + "int ov3d_g(int n, short k);\n")
+    with pytest.raises(_native.NativeError, match=r"short k"):
+        _native.read_header("typedef struct { int n; short k; } ov3d_u;\n" + good)
+    with pytest.raises(_native.NativeError, match=r"ov3d_h\(int n\)"):
+        _native.read_header(good + "unsigned ov3d_h(int n);\n")
+    with pytest.raises(_native.NativeError, match=r"w\[OV3D_UNKNOWN\]"):
+        _native.read_header("typedef struct { float w[OV3D_UNKNOWN]; } ov3d_v;\n")
+
+
+def test_missing_header_fails_loudly(monkeypatch):
+    from ov3d_amd import _native
+    monkeypatch.setattr(_native, "HEADER_PATH", "/nonexistent/ov3d.h")
+    with pytest.raises(_native.NativeError, match="/nonexistent/ov3d.h"):
+        _native._read_own_header()
 
 
 def test_version_string():

@@ -680,9 +680,10 @@ int ov3d_wgrad_bn(const void* dy, long long ldy, const void* x, long long ldx, i
                   float* workspace, int* counters, int nsplit, void* stream);
 long long ov3d_wgrad_workspace(int R, int N, int K, int nsplit);
 /* several independent weight gradients in one launch (+ one split reduction launch) per
- * 28 problems: the deferred dW / db of a backward pass (gemm.py).  256 x 256 tiles,
- * stream-K over (problem, tile, 32-row stage) units with one workgroup per CU; `nsplit`
- * is not used.  workspace: ov3d_wgrad_group_workspace() floats. */
+ * 512 problems: the deferred dW / db of a backward pass (gemm.py).  256 x 256 tiles,
+ * stream-K over (problem, tile, 64-row stage) units; `nsplit` is not used.  workspace:
+ * ov3d_wgrad_group_workspace() floats, 16-byte aligned: the launch's problem table (written
+ * by small launches of its own, so the call is safe to capture), then the partial slots. */
 typedef struct {
     const void* dy; long long ldy; const void* x; long long ldx;
     int R, N, K, nsplit;

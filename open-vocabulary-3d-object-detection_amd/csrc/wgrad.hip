@@ -17,13 +17,15 @@
 // over 8 waves (64 x 128 each), staged by LDS-DMA: a row stage of a 128 x 128 tile moves 64 flop per loaded
 // byte and the step's ~95 GFLOP of weight gradients were bound by the per-CU load path
 // (~12 B/cycle); 256 x 256 halves the bytes per flop.  Its work is split stream-K style:
-// the (problem, tile, 64-row stage) units of all problems, in order, are cut into one
-// equal range per CU; a workgroup flushes its accumulators at every tile boundary, straight
+// the (problem, tile, 64-row stage) units of all problems, in order, are cut into equal
+// ranges, one per CU for every 48 problems; a workgroup flushes its accumulators at every tile boundary, straight
 // into dW when it owns the whole tile, else into a partial slot that the reduction launch
-// adds in workgroup order (deterministic: the cut depends only on the problem list).
+// adds in workgroup order (deterministic: the cut depends only on the problem list and the
+// CU count).  The problem list of a launch is a table in the caller's workspace.
 #include <type_traits>
 #include <vector>
 
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "common.h"
@@ -549,9 +551,7 @@ __global__ void __launch_bounds__(256) wgrad_group128_reduce_kernel(WgradGroup12
 // Several independent weight gradients in one launch (the deferred dW / db of a whole
 // backward pass, gemm.py), stream-K over the units (problem, 256 x 256 tile, 64-row stage).
 constexpr int kSlot = TB * TB + TB;   // floats of one partial slot: tile + bias columns
-// a stream-K launch's problem: WgradArgs without the split fields, 32-bit strides (64 bytes),
-// so 48 problems fit the argument space (28 with WgradArgs: the step's ~100 deferred weight
-// gradients took 4 launches + 4 reductions)
+// a stream-K launch's problem: WgradArgs without the split fields, 32-bit strides (64 bytes)
 struct WgradSK {
     const bf16* dy;
     const bf16* x;
@@ -562,16 +562,43 @@ struct WgradSK {
     int vec_dy, vec_x;
 };
 static_assert(sizeof(WgradSK) == 64, "compact stream-K problem");
-constexpr int kSKMax = 48;   // problems per stream-K launch
-struct WgradGroup {
-    WgradSK p[kSKMax];
-    long long ubeg[kSKMax + 1];   // first unit of problem i
-    int sbeg[kSKMax + 1];         // first partial slot of problem i
-    int tbeg[kSKMax + 1];         // first tile of problem i (reduction grid)
+constexpr int kSKArgs = 46;   // problems one table-writer launch carries in its arguments
+constexpr int kSKCap = 512;   // problems per stream-K launch (the table lives in the workspace)
+constexpr int kSKCut = 48;    // problems per cut group
+constexpr int kSKCuts = (kSKCap + kSKCut - 1) / kSKCut;
+
+// The problem table of a stream-K launch, in the caller's workspace (device memory), and the
+// by-value header the kernels take.  Global tile gt = tbeg[i] + t of problem i owns the
+// partial slots [tslot[gt], tslot[gt + 1]): none when one workgroup owns the whole tile.
+// The cut: the launch's problems form groups of `cs` (the last one shorter); group c owns the
+// units [cu[c], cu[c + 1]) and cuts them into one equal range for each of its workgroups
+// [cw[c], cw[c + 1]), one per CU.  The groups are the launches of the time when a launch
+// took 48 problems by value: the ranges, and so every partial sum, are what they were.
+struct WgradTable {
+    WgradSK* rec;      // [n]
+    long long* ubeg;   // [n + 1] first unit of problem i
+    int* tbeg;         // [n + 1] first tile of problem i (reduction grid)
+    int* tslot;        // [T + 1] first partial slot of tile gt
+    int* tprob;        // [T] problem of tile gt
+    float* part;       // partial slots, kSlot floats each
+    long long U;       // units of the launch
     int n, G;
-    float* part;                  // partial slots, kSlot floats each
+    int cs, nc;        // problems per cut group, groups
+    int cw[kSKCuts + 1];
+    long long cu[kSKCuts + 1];
 };
-static_assert(sizeof(WgradGroup) <= 4000, "kernel argument space");
+// table writer: problems [first, first + cnt) of the table, as kernel arguments
+struct WgradWrite {
+    WgradSK p[kSKArgs];
+    long long ubeg[kSKArgs];
+    int tbeg[kSKArgs];
+    int sbeg[kSKArgs];   // first partial slot of the problem
+    WgradTable t;
+    int first, cnt;
+    int tiles, slots;    // totals: the closing prefix entries, stored by the last launch
+    int last;
+};
+static_assert(sizeof(WgradWrite) <= 4000, "kernel argument space");
 
 template <typename A>
 __host__ __device__ inline int sk_tiles_n(const A& a) { return (a.N + TB - 1) / TB; }
@@ -579,42 +606,104 @@ template <typename A>
 __host__ __device__ inline int sk_tiles(const A& a) { return sk_tiles_n(a) * ((a.K + TB - 1) / TB); }
 template <typename A>
 __host__ __device__ inline int sk_stages(const A& a) { return (a.R + BK - 1) / BK; }
+
 // first unit of workgroup w / the workgroup owning unit u (ranges floor(U w / G))
 __host__ __device__ inline long long sk_start(long long U, int G, int w) { return U * w / G; }
 __host__ __device__ inline int sk_owner(long long U, int G, long long u) {
     return (int)(((u + 1) * G - 1) / U);
 }
-// slots used by tile t of problem i (0 when one workgroup owns the whole tile)
-__host__ __device__ inline int sk_tile_slots(const WgradGroup& g, int i, int t, long long U) {
-    const int st = sk_stages(g.p[i]);
-    const long long uf = g.ubeg[i] + (long long)t * st, ul = uf + st - 1;
-    const int wf = sk_owner(U, g.G, uf), wl = sk_owner(U, g.G, ul);
+// slots used by tile t of a problem of st stages whose first unit is ub, counted from the
+// first unit of its cut group of U units and G workgroups (0 when one workgroup owns the
+// whole tile)
+__host__ __device__ inline int sk_tile_slots(long long ub, int st, int t, long long U, int G) {
+    const long long uf = ub + (long long)t * st, ul = uf + st - 1;
+    const int wf = sk_owner(U, G, uf), wl = sk_owner(U, G, ul);
     return wf == wl ? 0 : wl - wf + 1;
 }
 
-__global__ void __launch_bounds__(512, 1) wgrad_group_kernel(WgradGroup g) {
+// One thread per problem: its record and prefixes, and the slot base of each of its tiles.
+__global__ void __launch_bounds__(64) wgrad_group_table_kernel(WgradWrite w) {
+    static_assert(kSKArgs <= 64, "one thread per problem of the launch");
+    const int j = threadIdx.x;
+    if (j < w.cnt) {
+        const int i = w.first + j;
+        w.t.rec[i] = w.p[j];
+        w.t.ubeg[i] = w.ubeg[j];
+        w.t.tbeg[i] = w.tbeg[j];
+        const int st = sk_stages(w.p[j]), nt = sk_tiles(w.p[j]);
+        const int c = i / w.t.cs;
+        const long long cu = w.t.cu[c], cU = w.t.cu[c + 1] - cu;
+        const int cG = w.t.cw[c + 1] - w.t.cw[c];
+        int slot = w.sbeg[j];
+        for (int t = 0; t < nt; ++t) {
+            w.t.tslot[w.tbeg[j] + t] = slot;
+            w.t.tprob[w.tbeg[j] + t] = i;
+            slot += sk_tile_slots(w.ubeg[j] - cu, st, t, cU, cG);
+        }
+    }
+    if (w.last && j == 0) {
+        w.t.ubeg[w.t.n] = w.t.U;
+        w.t.tbeg[w.t.n] = w.tiles;
+        w.t.tslot[w.tiles] = w.slots;
+    }
+}
+
+// The table is written by earlier launches and only read here: reads through the constant
+// address space stay scalar loads (the index is workgroup-uniform).
+#define SK_CONST __attribute__((address_space(4)))
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ WgradSK sk_rec(const WgradSK* rec, int i) {
+    struct { i32x4 q[4]; } v;
+    const SK_CONST i32x4* p = (const SK_CONST i32x4*)(uintptr_t)(rec + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v.q[k] = p[k];
+    return __builtin_bit_cast(WgradSK, v);
+}
+template <typename T>
+__device__ __forceinline__ T sk_ld(const T* p, int i) {
+    return ((const SK_CONST T*)(uintptr_t)p)[i];
+}
+
+__global__ void __launch_bounds__(512, 1) wgrad_group_kernel(WgradTable g) {
     // all LDS in ONE array: dy / x images of the two stages
     __shared__ __attribute__((aligned(16))) bf16 L[4 * STG];
-    const long long U = g.ubeg[g.n];
+    static_assert(kSKCap <= 512, "the first problem is found by one compare per thread");
     const int w = blockIdx.x;
-    long long u = sk_start(U, g.G, w);
-    const long long u1 = sk_start(U, g.G, w + 1);
-    int i = 0;
+    int c = 0;
+    while (w >= g.cw[c + 1]) ++c;
+    const int w0 = g.cw[c], cG = g.cw[c + 1] - w0;
+    const long long cu = g.cu[c], cU = g.cu[c + 1] - cu;
+    long long u = cu + sk_start(cU, cG, w - w0);
+    const long long u1 = cu + sk_start(cU, cG, w - w0 + 1);
+    // problem of the first unit: every problem has units, so it is the last one whose first
+    // unit is <= u (one compare per thread, counted over the workgroup)
+    int* cnt = reinterpret_cast<int*>(L);
+    {
+        const int tid = threadIdx.x;
+        const bool le = tid < g.n && g.ubeg[tid] <= u;
+        const unsigned long long m = __ballot(le);
+        if ((tid & 63) == 0) cnt[tid >> 6] = __popcll(m);
+    }
+    __syncthreads();
+    int i = -1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) i += cnt[k];
+    i = __builtin_amdgcn_readfirstlane(i);   // wgrad_seg256's opening barrier covers cnt
     while (u < u1) {
-        while (u >= g.ubeg[i + 1]) ++i;
-        const WgradSK& a = g.p[i];
+        while (u >= sk_ld(g.ubeg, i + 1)) ++i;
+        const WgradSK a = sk_rec(g.rec, i);
         const int st = sk_stages(a), tn = sk_tiles_n(a);
-        const long long local = u - g.ubeg[i];
+        const long long ub = sk_ld(g.ubeg, i);
+        const long long local = u - ub;
         const int t = (int)(local / st), s0 = (int)(local - (long long)t * st);
         const int s1 = (int)min((long long)st, s0 + (u1 - u));
         const int rbeg = s0 * BK, rend = min(a.R, s1 * BK);
-        const long long uf = g.ubeg[i] + (long long)t * st;
-        const int wf = sk_owner(U, g.G, uf), wl = sk_owner(U, g.G, uf + st - 1);
-        if (wf == wl) {
+        const int gt = sk_ld(g.tbeg, i) + t;
+        const int slot = sk_ld(g.tslot, gt), nsl = sk_ld(g.tslot, gt + 1) - slot;
+        if (nsl == 0) {
             wgrad_seg256(a, t % tn, t / tn, rbeg, rend, a.dW, a.ldw, false, a.db, L);
         } else {
-            int slot = g.sbeg[i];
-            for (int tt = 0; tt < t; ++tt) slot += sk_tile_slots(g, i, tt, U);
+            const int wf = w0 + sk_owner(cU, cG, ub + (long long)t * st - cu);
             float* ps = g.part + (size_t)(slot + (w - wf)) * kSlot;
             wgrad_seg256(a, t % tn, t / tn, rbeg, rend, ps, TB, true, ps + TB * TB, L);
         }
@@ -624,17 +713,13 @@ __global__ void __launch_bounds__(512, 1) wgrad_group_kernel(WgradGroup g) {
 
 // split tiles: dW / db = the tile's partial slots summed in workgroup order.  Block b: tile
 // b / 65 (all tiles of the launch), part b % 65 (64 x 1024 tile elements, then the bias)
-__global__ void __launch_bounds__(256) wgrad_group_reduce_kernel(WgradGroup g) {
-    const long long U = g.ubeg[g.n];
+__global__ void __launch_bounds__(256) wgrad_group_reduce_kernel(WgradTable g) {
     const int gt = blockIdx.x / 65, sub = blockIdx.x - gt * 65;
-    int i = 0;
-    while (i + 1 < g.n && gt >= g.tbeg[i + 1]) ++i;
-    const WgradSK& a = g.p[i];
-    const int t = gt - g.tbeg[i];
-    const int nsl = sk_tile_slots(g, i, t, U);
+    const int slot = sk_ld(g.tslot, gt), nsl = sk_ld(g.tslot, gt + 1) - slot;
     if (nsl == 0) return;
-    int slot = g.sbeg[i];
-    for (int tt = 0; tt < t; ++tt) slot += sk_tile_slots(g, i, tt, U);
+    const int i = sk_ld(g.tprob, gt);
+    const WgradSK a = sk_rec(g.rec, i);
+    const int t = gt - sk_ld(g.tbeg, i);
     const int tn = sk_tiles_n(a);
     const int n0 = (t % tn) * TB, k0 = (t / tn) * TB;
     const float* ps = g.part + (size_t)slot * kSlot;
@@ -764,7 +849,7 @@ extern "C" int ov3d_wgrad_bn(const void* dy, long long ldy, const void* x, long 
                         stream);
 }
 
-// stream-K plan of problems [first, first + g.n): units, slot and tile prefixes, grid
+// CUs of the device, or the workgroup count OV3D_WGRAD_WGS asks for
 static int cu_count() {
     static int cus = 0;
     if (cus == 0) {
@@ -774,8 +859,7 @@ static int cu_count() {
             cus = n;
         else
             cus = 256;
-        // OV3D_WGRAD_WGS: workgroups of the stream-K launch (measurement knob; default one
-        // per CU)
+        // OV3D_WGRAD_WGS: workgroups of a cut group (measurement knob; default one per CU)
         if (const char* e = getenv("OV3D_WGRAD_WGS")) {
             const int v = atoi(e);
             if (v > 0) cus = v;
@@ -784,31 +868,67 @@ static int cu_count() {
     return cus;
 }
 
-// problems per stream-K launch: kSKMax; OV3D_WGRAD_SK_MAX (1 .. kSKMax) for A/B runs (28: the
-// round-5 split)
+// problems per stream-K launch: every problem of the call, up to kSKCap, in cut groups of
+// kSKCut.  OV3D_WGRAD_SK_MAX (1 .. kSKCap) for A/B runs: a launch and a reduction of their own
+// for every so many problems, each one cut group (48: the three launches + three reductions
+// per SUN step of the by-value launches; 28: the round-5 split)
+static bool sk_chunked = false;
 static int sk_max() {
     static int m = 0;
     if (!m) {
-        m = kSKMax;
+        m = kSKCap;
         if (const char* e = getenv("OV3D_WGRAD_SK_MAX")) {
             const int v = atoi(e);
-            if (v >= 1 && v <= kSKMax) m = v;
+            if (v >= 1 && v <= kSKCap) {
+                m = v;
+                sk_chunked = true;
+            }
         }
     }
     return m;
 }
+static int sk_cut() { return sk_chunked ? sk_max() : kSKCut; }
 
 static bool sk_ok(const ov3d_wgrad_problem& q) {
     (void)q;   // every problem: the stream-K kernel loads unaligned / narrow rows per element
     return true;
 }
 
-// stream-K plan of the problems idx[first .. first + g.n): units, slot and tile prefixes, grid
-static int plan_group(WgradGroup& g, const ov3d_wgrad_problem* probs, const int* idx, int first,
-                      int n, long long& slots) {
+// stream-K plan of one launch: records, unit / tile / slot prefixes per problem, grid
+struct SKPlan {
+    std::vector<WgradSK> p;
+    std::vector<long long> ubeg;
+    std::vector<int> tbeg, sbeg;
+    std::vector<long long> cu;   // cut groups: first unit, first workgroup
+    std::vector<int> cw;
+    long long U;
+    int n, G, cs, nc, tiles, split_tiles, slots;
+};
+
+// byte offsets of the table's arrays (each 16-byte aligned) and its size
+struct SKTable {
+    size_t rec, ubeg, tbeg, tslot, tprob, bytes;
+};
+static SKTable table_layout(int n, int tiles) {
+    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+    SKTable t;
+    t.rec = 0;
+    t.ubeg = up((size_t)n * sizeof(WgradSK));
+    t.tbeg = t.ubeg + up((size_t)(n + 1) * sizeof(long long));
+    t.tslot = t.tbeg + up((size_t)(n + 1) * sizeof(int));
+    t.tprob = t.tslot + up((size_t)(tiles + 1) * sizeof(int));
+    t.bytes = t.tprob + up((size_t)tiles * sizeof(int));
+    return t;
+}
+
+// plan of the problems idx[first .. first + g.n)
+static int plan_group(SKPlan& g, const ov3d_wgrad_problem* probs, const int* idx, int first, int n) {
     g.n = n - first < sk_max() ? n - first : sk_max();
-    long long U = 0;
-    int tiles = 0;
+    g.p.resize(g.n);
+    g.ubeg.resize(g.n);
+    g.tbeg.resize(g.n);
+    g.sbeg.resize(g.n);
+    long long U = 0, tiles = 0;
     for (int j = 0; j < g.n; ++j) {
         const ov3d_wgrad_problem& q = probs[idx[first + j]];
         WgradArgs f;
@@ -819,25 +939,43 @@ static int plan_group(WgradGroup& g, const ov3d_wgrad_problem* probs, const int*
         g.p[j] = WgradSK{f.dy, f.x, f.dW, f.db, (int)f.ldy, (int)f.ldx, (int)f.ldw, f.R, f.N, f.K,
                          f.vec_dy, f.vec_x};
         g.ubeg[j] = U;
-        g.tbeg[j] = tiles;
+        g.tbeg[j] = (int)tiles;
         U += (long long)sk_tiles(g.p[j]) * sk_stages(g.p[j]);
         tiles += sk_tiles(g.p[j]);
+        if (tiles * 65 >= (1LL << 31)) return OV3D_EINVAL;   // the reduction's grid
     }
-    g.ubeg[g.n] = U;
-    g.tbeg[g.n] = tiles;
-    g.G = (int)(U < cu_count() ? U : cu_count());
-    int sl = 0;
+    g.U = U;
+    g.tiles = (int)tiles;
+    g.cs = sk_cut();
+    g.nc = (g.n + g.cs - 1) / g.cs;
+    g.cu.assign(g.nc + 1, U);
+    g.cw.assign(g.nc + 1, 0);
+    for (int c = 0; c < g.nc; ++c) g.cu[c] = g.ubeg[c * g.cs];
+    for (int c = 0; c < g.nc; ++c) {
+        const long long cU = g.cu[c + 1] - g.cu[c];
+        g.cw[c + 1] = g.cw[c] + (int)(cU < cu_count() ? cU : cu_count());
+    }
+    g.G = g.cw[g.nc];
+    long long sl = 0;
+    g.split_tiles = 0;
     for (int j = 0; j < g.n; ++j) {
-        g.sbeg[j] = sl;
-        for (int t = 0; t < sk_tiles(g.p[j]); ++t) sl += sk_tile_slots(g, j, t, U);
+        g.sbeg[j] = (int)sl;
+        const int st = sk_stages(g.p[j]), c = j / g.cs;
+        for (int t = 0; t < sk_tiles(g.p[j]); ++t) {
+            const int k = sk_tile_slots(g.ubeg[j] - g.cu[c], st, t, g.cu[c + 1] - g.cu[c],
+                                        g.cw[c + 1] - g.cw[c]);
+            sl += k;
+            g.split_tiles += k > 0;
+        }
     }
-    g.sbeg[g.n] = sl;
-    slots = sl;
+    g.slots = (int)sl;
     return OV3D_OK;
 }
 
-// workspace floats: [stream-K partial slots of the largest launch | fallback split partials]
-static long long group_space(const ov3d_wgrad_problem* probs, int n, long long* sk_part) {
+// workspace floats: [problem table of the largest launch | stream-K partial slots of the
+// largest launch | fallback split partials]
+static long long group_space(const ov3d_wgrad_problem* probs, int n, long long* table,
+                             long long* sk_part) {
     std::vector<int> sk;
     long long fb = 0;
     for (int i = 0; i < n; ++i) {
@@ -845,21 +983,24 @@ static long long group_space(const ov3d_wgrad_problem* probs, int n, long long* 
         else fb += ov3d_wgrad_workspace(probs[i].R, probs[i].N, probs[i].K, probs[i].nsplit);
     }
     long long most = 0;
+    size_t tab = 0;
+    SKPlan g;
     for (int first = 0; first < (int)sk.size(); first += sk_max()) {
-        WgradGroup g;
-        long long slots = 0;
-        if (plan_group(g, probs, sk.data(), first, (int)sk.size(), slots) != OV3D_OK) return -1;
-        most = slots > most ? slots : most;
+        if (plan_group(g, probs, sk.data(), first, (int)sk.size()) != OV3D_OK) return -1;
+        most = g.slots > most ? g.slots : most;
+        const size_t b = table_layout(g.n, g.tiles).bytes;
+        tab = b > tab ? b : tab;
     }
+    *table = (long long)(tab / sizeof(float));
     *sk_part = most * kSlot;
-    return most * kSlot + fb;
+    return *table + most * kSlot + fb;
 }
 
 /* floats of workspace for ov3d_wgrad_group (the launches of one call run in stream order) */
 extern "C" long long ov3d_wgrad_group_workspace(const ov3d_wgrad_problem* probs, int n) {
     if (!probs || n <= 0) return 0;
-    long long skp = 0;
-    const long long w = group_space(probs, n, &skp);
+    long long tab = 0, skp = 0;
+    const long long w = group_space(probs, n, &tab, &skp);
     return w < 0 ? 0 : w;
 }
 
@@ -867,27 +1008,66 @@ extern "C" int ov3d_wgrad_group(const ov3d_wgrad_problem* probs, int n, float* w
                                 void* stream) {
     if (!probs || n <= 0) return OV3D_EINVAL;
     hipStream_t st = ov3d_stream(stream);
-    long long skp = 0;
-    const long long need = group_space(probs, n, &skp);
+    long long tab = 0, skp = 0;
+    const long long need = group_space(probs, n, &tab, &skp);
     if (need < 0) return OV3D_EINVAL;
-    if (need > 0 && !workspace) return OV3D_EINVAL;
+    if (need > 0 && (!workspace || (uintptr_t)workspace % 16 != 0)) return OV3D_EINVAL;
+    // OV3D_WGRAD_PLAN=1: the plan of every stream-K launch on stderr
+    static const bool show = getenv("OV3D_WGRAD_PLAN") != nullptr;
     std::vector<int> sk, fb;
     for (int i = 0; i < n; ++i) (sk_ok(probs[i]) ? sk : fb).push_back(i);
+    SKPlan g;
     for (int first = 0; first < (int)sk.size(); first += sk_max()) {
-        WgradGroup g;
-        long long slots = 0;
-        const int rc = plan_group(g, probs, sk.data(), first, (int)sk.size(), slots);
+        const int rc = plan_group(g, probs, sk.data(), first, (int)sk.size());
         if (rc != OV3D_OK) return rc;
-        g.part = workspace;
+        if (show)
+            fprintf(stderr, "wgrad_group plan: problems %d units %lld cut groups %d workgroups %d tiles %d split %d slots %d\n",
+                    g.n, g.U, g.nc, g.G, g.tiles, g.split_tiles, g.slots);
         if (g.G <= 0) continue;
-        wgrad_group_kernel<<<g.G, 512, 0, st>>>(g);
+        // The table goes through kernel arguments (kSKArgs problems a launch), not a copy
+        // from host memory: a captured graph replays the writes with the arguments it
+        // recorded, and the workspace is a fresh allocation on every call.
+        const SKTable lay = table_layout(g.n, g.tiles);
+        char* tb = reinterpret_cast<char*>(workspace);
+        WgradWrite w;
+        w.t.rec = reinterpret_cast<WgradSK*>(tb + lay.rec);
+        w.t.ubeg = reinterpret_cast<long long*>(tb + lay.ubeg);
+        w.t.tbeg = reinterpret_cast<int*>(tb + lay.tbeg);
+        w.t.tslot = reinterpret_cast<int*>(tb + lay.tslot);
+        w.t.tprob = reinterpret_cast<int*>(tb + lay.tprob);
+        w.t.part = workspace + tab;
+        w.t.U = g.U;
+        w.t.n = g.n;
+        w.t.G = g.G;
+        w.t.cs = g.cs;
+        w.t.nc = g.nc;
+        for (int c = 0; c <= kSKCuts; ++c) {
+            w.t.cu[c] = g.cu[c < g.nc ? c : g.nc];
+            w.t.cw[c] = g.cw[c < g.nc ? c : g.nc];
+        }
+        w.tiles = g.tiles;
+        w.slots = g.slots;
+        for (int f0 = 0; f0 < g.n; f0 += kSKArgs) {
+            w.first = f0;
+            w.cnt = g.n - f0 < kSKArgs ? g.n - f0 : kSKArgs;
+            w.last = f0 + w.cnt == g.n;
+            for (int j = 0; j < w.cnt; ++j) {
+                w.p[j] = g.p[f0 + j];
+                w.ubeg[j] = g.ubeg[f0 + j];
+                w.tbeg[j] = g.tbeg[f0 + j];
+                w.sbeg[j] = g.sbeg[f0 + j];
+            }
+            wgrad_group_table_kernel<<<1, 64, 0, st>>>(w);
+            OV3D_LAUNCH_CHECK();
+        }
+        wgrad_group_kernel<<<g.G, 512, 0, st>>>(w.t);
         OV3D_LAUNCH_CHECK();
-        if (slots > 0) {
-            wgrad_group_reduce_kernel<<<g.tbeg[g.n] * 65, 256, 0, st>>>(g);
+        if (g.slots > 0) {
+            wgrad_group_reduce_kernel<<<g.tiles * 65, 256, 0, st>>>(w.t);
             OV3D_LAUNCH_CHECK();
         }
     }
-    long long woff = skp;
+    long long woff = tab + skp;
     for (int first = 0; first < (int)fb.size(); first += kGroupMax) {
         WgradGroup128 g;
         g.n = (int)fb.size() - first < kGroupMax ? (int)fb.size() - first : kGroupMax;

@@ -216,6 +216,15 @@ __device__ __forceinline__ float bf16_lo(float x) {
     return __builtin_isinf(x) ? 0.f : x - bf16_hi(x);
 }
 
+// the forward's running max as the matrix cores subtract it: one bf16 below kStabBig (every
+// score range the training step sees; bit-identical to the one-term form), bf16 hi + lo
+// (exact in fp32, 2^-16 relative) from there on
+constexpr float kStabBig = 32768.f;
+__device__ __forceinline__ float stabiliser(float x) {
+    const float hi = bf16_hi(x);
+    return fabsf(x) < kStabBig ? hi : hi + bf16_hi(bf16_lo(x));
+}
+
 // online-softmax rescale only when a query's running max grows by more than this
 // (log2 units): P stays <= 2^8 between rescales (cdna_hip_programming.md T13)
 constexpr float RESCALE_THR = 8.f;
@@ -441,7 +450,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
     // of the matrix cores; the first tile with an attended key sets it to that tile's max
     float mb = 0.f;
     bool unset = true;
-    const bf16x8 k1 = kslots(1.f, 0.f, h == 0);
+    const bf16x8 k1 = kslots(1.f, 1.f, h == 0);
     bf16x8 kmb = kslots(0.f, 0.f, false);
     // row sums on the matrix cores: an all-ones A operand times the (undropped) P^T packs
     // gives every accumulator row the column sums = each lane's query row sum over the 64 keys
@@ -533,7 +542,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
             if (__any(mx > RESCALE_THR || (unset && seen))) {
                 // new stabiliser: the running max rounded to bf16 (nearest: never below mb when
                 // mx > 0); a query's first attended tile sets it up or down
-                const float mn = (mx > 0.f || (unset && seen)) ? bf16_hi(mb + mx) : mb;
+                // A max of 2^15 or more takes a second bf16 term (k-slot 1): one bf16 alone is
+                // off by up to 2^-9 of it, and past ~2^16 that put exp2(S - mb) at +inf and
+                // the row at inf / inf (eval on activations of ~1e5: NaN where SDPA is finite)
+                const float mn = (mx > 0.f || (unset && seen)) ? stabiliser(mb + mx) : mb;
                 const float d = mn - mb;
                 // o and the sums of a query with no attended key yet are zero (alpha = 1 keeps
                 // them so even when exp2(-d) would overflow)
@@ -549,7 +561,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) st[t][i] -= d;
                 mb = mn;
-                kmb = kslots(-mb, 0.f, h == 0);
+                // (mb is finite: a sum of finite scores; this form keeps the kernels' register
+                // budget, bf16_lo's infinity test cost the masked hashing variant two spills)
+                const float mbh = bf16_hi(mb);
+                kmb = kslots(-mbh, mbh - mb, h == 0);
                 unset = unset && !seen;
             }
             // p = exp2(S - mb), one bf16 pack per key pair; dropout zeroes p after the row sum.

@@ -13,7 +13,10 @@ import contextlib
 import numpy as np
 import torch
 
-from helpers import batch_from_fixture, fixture, fixture_args, fixture_prefix, pin_matcher
+import functools
+
+from helpers import (batch_from_fixture, fixture, fixture_args, fixture_parts, fixture_prefix,
+                     pin_matcher)
 import det_init  # noqa: E402  (tests/golden, on the path through helpers)
 from fake_clip import FakeRegionCLIP  # noqa: E402
 
@@ -27,15 +30,42 @@ BF16_TOL = dict(out=5e-2, loss=3e-2, grad_norm=5e-2, grad=1e-1, grad_proj=1e-1)
 BF16_GRAD_FLOOR = 1e-3   # bf16: gradients below this fraction of the total norm count as zero
 
 
-def build(fx, device, dataset):
+# (the _full fixture, its eval-mode twin, dataset)
+EVAL_CASES = [("model_sun_full.npz", "model_sun_eval.npz", "sunrgbd"),
+              ("model_scannet_full.npz", "model_scannet_eval.npz", "scannet")]
+INPUT_KEYS = ("point_clouds", "point_cloud_dims_min", "point_cloud_dims_max")
+
+
+def build(fx, device, dataset, train=True, args=None, seed=None, load_bn=True):
+    """the product model with the fixture's det_init weights.  Defaults: the fixture's args and
+    seed, train mode.  train=False: eval mode; a fixture with bn/ entries (the eval fixtures)
+    gets those running statistics loaded unless load_bn is False."""
     from ov3d_amd.dataset_config import CONFIGS
     from ov3d_amd.model_3detr import build_3detr
-    args = fixture_args(fx)
+    args = fixture_args(fx) if args is None else args
     cfg = CONFIGS[dataset]()
     model, _ = build_3detr(args, cfg, text_embedding=torch.from_numpy(fx["text"]))
-    filled = det_init.fill_(model, int(fx["seed"]))
+    filled = det_init.fill_(model, int(fx["seed"]) if seed is None else seed)
     assert filled == sorted(str(x) for x in fx["filled"]), "state-dict keys differ from the reference"
-    return model.to(device).train(), cfg, args
+    bn = fixture_prefix(fx, "bn/") if load_bn else {}
+    if bn:
+        sd = model.state_dict(keep_vars=True)
+        assert set(bn) == {k for k in sd if k.endswith(("running_mean", "running_var"))}
+        with torch.no_grad():
+            for k, v in bn.items():
+                sd[k].copy_(torch.from_numpy(v))
+    return model.to(device).train(train), cfg, args
+
+
+@functools.lru_cache(maxsize=None)
+def eval_fixture(name_full, name_eval):
+    """the eval-mode fixture plus the inputs, text embedding, seed and key list of its _full
+    sibling (stored once); read-only, shared by the tests"""
+    fx = fixture_parts(name_eval)
+    for k, v in fixture(name_full).items():
+        if k.startswith("in/") or k in ("text", "seed", "filled"):
+            fx[k] = v
+    return fx
 
 
 def rel(a, b):
@@ -153,6 +183,70 @@ def run(name, dataset, device, amp=None, f64=False, grad_floor=None):
         den = max(float(np.linalg.norm(ref)), floor)
         rep["grad"].append((float(np.linalg.norm(g.astype(np.float64) - ref)) / den, n))
     return {k: sorted(v, reverse=True) for k, v in rep.items()}
+
+
+def eval_batch(fx, device, scenes=None, f64=False):
+    batch = batch_from_fixture(fx, device)
+    if scenes is not None:
+        batch = {k: v[scenes] for k, v in batch.items()}
+    if f64:
+        batch = {k: (v.double() if v.is_floating_point() else v) for k, v in batch.items()}
+    return batch
+
+
+def eval_forward(model, batch, amp=None, no_grad=True):
+    """the inference forward: the model as it stands (eval mode) on the batch's inputs"""
+    inputs = {k: batch[k] for k in INPUT_KEYS}
+    with torch.no_grad() if no_grad else contextlib.nullcontext():
+        with torch.autocast("cuda", dtype=amp or torch.float32, enabled=amp is not None):
+            return model(inputs)
+
+
+def layers_of(out):
+    return [out["outputs"]] + out["aux_outputs"]
+
+
+def eval_out_report(fx, out, rep, scenes=None):
+    for li, lay in enumerate(layers_of(out)):
+        for k, ref in fixture_prefix(fx, f"out/{li}/").items():
+            ref = ref if scenes is None else ref[scenes]
+            got = lay[k].detach().double().cpu().numpy()
+            assert got.shape == ref.shape, (li, k, got.shape, ref.shape)
+            rep["out"].append((rel(got, ref), f"{li}/{k}"))
+            rep["out_l2"].append((float(np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-30)),
+                                  f"{li}/{k}"))
+
+
+def run_eval(fx, dataset, device, amp=None, f64=False, scenes=None, model=None):
+    """eval twin of run: model.eval() under no_grad on the eval fixture `fx` (eval_fixture), its
+    args (the reference's dropouts on) and bn/ running statistics; the criterion as evaluate()
+    calls it, on the recorded matching.  -> (report with out / out_l2 / loss, the outputs).
+    scenes: rows of the batch to run alone (outputs only: the fixture's losses are B = 2's)"""
+    from ov3d_amd.criterion import build_criterion
+    args = fixture_args(fx)
+    if model is None:
+        model, cfg, args = build(fx, device, dataset, train=False)
+    else:
+        from ov3d_amd.dataset_config import CONFIGS
+        cfg = CONFIGS[dataset]()
+    assert not model.training
+    batch = eval_batch(fx, device, scenes, f64)
+    if f64:
+        model = model.double()
+    rep = {"out": [], "out_l2": [], "loss": []}
+    with float64_host() if f64 else contextlib.nullcontext():
+        out = eval_forward(model, batch, amp)
+        eval_out_report(fx, out, rep, scenes)
+        if scenes is None:
+            with torch.no_grad():
+                crit = pin_matcher(build_criterion(args, cfg).to(device), fx, device)
+                loss, ld = crit(out, dict(batch), clip=FakeRegionCLIP())
+            ref_ld = fixture_prefix(fx, "ld/")
+            assert set(ld) == set(ref_ld), set(ld) ^ set(ref_ld)
+            for k, v in ref_ld.items():
+                rep["loss"].append((abs(ld[k].item() - float(v)) / max(abs(float(v)), 1e-3), k))
+            rep["loss"].append((abs(loss.item() - float(fx["loss"])) / abs(float(fx["loss"])), "loss"))
+    return {k: sorted(v, reverse=True) for k, v in rep.items()}, out
 
 
 def worst(rep, k):

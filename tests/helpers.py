@@ -24,6 +24,27 @@ def fixture(name):
     return dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
 
 
+def fixture_parts(name):
+    """a fixture written as NAME.npz + NAME.pN.npz (make_golden.py save_parts: every committed
+    file under 1 MiB); arrays split along axis 0 into KEY#i are put back together"""
+    stem = name[:-4]
+    files = [name] + sorted(f for f in os.listdir(GOLDEN) if f.startswith(stem + ".p") and f.endswith(".npz"))
+    raw = {}
+    for f in files:
+        raw.update(fixture(f))
+    fx, pieces = {}, {}
+    for k, v in raw.items():
+        if "#" in k:
+            base, i = k.rsplit("#", 1)
+            pieces.setdefault(base, {})[int(i)] = v
+        else:
+            fx[k] = v
+    for base, ps in pieces.items():
+        assert sorted(ps) == list(range(len(ps))), (base, sorted(ps))
+        fx[base] = np.concatenate([ps[i] for i in range(len(ps))])
+    return fx
+
+
 def fixture_args(fx):
     items = ast.literal_eval(str(fx["args"]))
     return argparse.Namespace(**dict(items))

@@ -55,6 +55,28 @@ def test_product_float64_equals_reference_float64(shim, name, ds):
         assert err <= F64_TOL, (group, key, err)
 
 
+@pytest.mark.parametrize("name,name_eval,ds", F.EVAL_CASES)
+def test_product_float64_eval_equals_reference_float64(shim, name, name_eval, ds):
+    """the inference forward (model.eval() under no_grad, the reference's dropouts on, running
+    statistics far from the batch's own: model_*_eval.npz) and the criterion as evaluate() calls
+    it: the product's host code in float64 equals the float64 reference on every output of all
+    8 layers and all 56 losses"""
+    torch.set_num_threads(8)
+    fx = F.eval_fixture(name, name_eval)
+    # the fixture is not blind: train-mode outputs differ by >= 10x the fp32 bar on every key
+    tve = {k: float(v) for k, v in fx.items() if k.startswith("train_vs_eval/0/")}
+    # (but a key that is identically zero in both modes: ScanNet's angle_continuous)
+    exempt = [k for k in str(fx["train_vs_eval_exempt"]).split(",") if k]
+    assert exempt == (["angle_continuous"] if ds == "scannet" else []), exempt
+    assert len(tve) == 12 - len(exempt) and min(tve.values()) >= 10 * F.FP32_TOL, tve
+    rep, _ = F.run_eval(fx, ds, "cpu", f64=True)
+    assert len(rep["loss"]) == 57
+    assert len(rep["out"]) == 8 * 11 + 1   # 11 keys per layer + the final layer's visual_embeds
+    for group in rep:
+        err, key = F.worst(rep, group)
+        assert err <= F64_TOL, (group, key, err)
+
+
 def _record(kind, name, obj):
     """append a measured figure to the JSON-lines file OV3D_PARITY_RECORD names (the GPU runs
     whose figures are kept under profiles/)"""

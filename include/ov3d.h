@@ -310,9 +310,17 @@ int ov3d_bn_relu_bwd_cin(int pass, const void* dz, const void* y, const float* s
  *   boxes (B,K,stride) f64 rows [x1,y1,z1,x2,y2,z2,score(,cls)], stride 7|8
  *   valid (B,K) uint8 or NULL: rows with 0 do not take part (nonempty mask)
  *   keep_out (B,K) uint8 (1 = picked).  samecls: suppress only same class.
- * Ties in score: larger index first (== np.argsort(kind="stable")).  K <= 512. */
+ * Ties in score: larger index first (== np.argsort(kind="stable")).  K <= 2048: up to 512
+ * the K x K suppression mask is built in LDS, above it the rows are tested during the walk
+ * (same result; no workspace either way). */
 int ov3d_nms3d(const double* boxes, const uint8_t* valid, int B, int K, int stride, double thr,
                int old_type, int samecls, uint8_t* keep_out, void* stream);
+
+/* ov3d_nms3d and ov3d_ap_match pick their kernel by shape (ov3d_nms3d: K <= 512 / K <= 2048;
+ * ov3d_ap_match: K <= 256 and G <= 64 / K <= 2048 and G <= 1024).  on = 1 runs the large-shape
+ * kernels at every shape (tests: bit-equal results), 0 restores the dispatch, -1 only
+ * queries; returns the previous setting (host-only, default 0). */
+int ov3d_eval_large_kernels(int on);
 
 /* NMS box table straight from predicted corners (ap_calculator.py:153-190):
  *   corners (B,K,8,3) f32, obj (B,K) f32, cls (B,K) int64 -> boxes (B,K,8) f64 */
@@ -1130,7 +1138,8 @@ int ov3d_rows_gather(const void* feat, long long rows_per_scene, long long row_b
  *     -> iou (S,K,G) f64 (0 where either is invalid)
  *   ov3d_ap_match: eval_det_cls's TP/FP walk (eval_det.py:104-131) per (scene, class):
  *     scores (S,K,C) f32 (-inf: not a detection of that class), gt_cls (S,G) int64 ->
- *     tp (S,K,C) u8 (1 TP, 0 FP) for every detection; K <= 256, G <= 64
+ *     tp (S,K,C) u8 (1 TP, 0 FP) for every detection; K <= 2048, G <= 1024 (one thread per
+ *     (scene, class) up to K 256 and G 64, one workgroup above)
  *   ov3d_ap_curve: voc_ap (eval_det.py:20-52, 133-146) per class from the detections' TP flags
  *     in global descending-confidence order, tp_sorted (C, M) u8 with nvalid (C) leading
  *     entries valid, npos (C) GT counts; tp_pos (C, tp_cap) int32 workspace

@@ -29,10 +29,12 @@ import torch
 from . import _native as nat
 from . import nms as _nms
 
-# ov3d_ap_match limits (csrc/evaldet.hip): proposals walked per (scene, class), and the
-# per-scene "detected" flags of the GT boxes in one 64-bit word
-AP_MAX_PROPOSALS = 256
-AP_MAX_GT = 64
+# ov3d_ap_match limits (csrc/evaldet.hip): proposals and GT boxes per scene.  Up to 256 / 64
+# one thread walks a (scene, class); above that a workgroup does (same TP flags).  2048 is the
+# most queries a model can have (the encoders emit at most 2048 points), 1024 ov3d_hungarian's
+# bound on the GT boxes.
+AP_MAX_PROPOSALS = 2048
+AP_MAX_GT = 1024
 
 
 def get_ap_config_dict(remove_empty_box=True, use_3d_nms=True, nms_iou=0.25, use_old_type_nms=False,
@@ -80,7 +82,14 @@ def parse_predictions_device(predicted_boxes, sem_cls_probs, objectness_probs, p
     if config_dict.get("no_nms", False):
         pred_mask = nonempty
     elif not config_dict["use_3d_nms"]:
-        raise NotImplementedError("2D NMS (use_3d_nms=False) is not on the 3DETR path")
+        # nms_2d_faster on the bird's-eye rectangles (ap_calculator.py:89-116): min / max of the
+        # upright-camera x and z, as rows of unit depth for the 3D kernel
+        c64 = corners.double()
+        lo, hi = c64.amin(2), c64.amax(2)
+        table = torch.stack([lo[..., 0], lo[..., 2], hi[..., 0], hi[..., 2], obj.double()], -1)
+        keep = _nms.nms3d_batched(_nms.boxes2d_as_3d(table), config_dict["nms_iou"],
+                                  config_dict["use_old_type_nms"], samecls=False, valid=nonempty)
+        pred_mask = keep.bool()
     else:
         boxes = _nms.nms_boxes_from_corners(corners, obj, pred_cls if config_dict["cls_nms"] else None)
         keep = _nms.nms3d_batched(boxes, config_dict["nms_iou"], config_dict["use_old_type_nms"],
@@ -134,8 +143,6 @@ def eval_det_device(scores, corners, gt_corners, gt_cls, gt_present, ovthresh_li
     S, K, C = scores.shape
     G = gt_corners.shape[1]
     if K > AP_MAX_PROPOSALS or G > AP_MAX_GT:
-        # ov3d_ap_match keeps one 64-bit "detected" word per GT block and walks <= 256
-        # proposals per (scene, class) thread
         raise ValueError(f"device AP supports <= {AP_MAX_PROPOSALS} proposals and <= {AP_MAX_GT} "
                          f"GT boxes per scene (got K={K}, G={G}); nqueries / max_num_obj too large")
     dev = scores.device
@@ -209,6 +216,11 @@ class APCalculator:
 
     def step(self, predicted_box_corners, sem_cls_probs, objectness_probs, point_cloud,
              gt_box_corners, gt_box_sem_cls_labels, gt_box_present):
+        K, G = predicted_box_corners.shape[1], gt_box_corners.shape[1]
+        if K > min(AP_MAX_PROPOSALS, _nms.MAX_K) or G > AP_MAX_GT:
+            # here, not after the whole pass in compute_metrics
+            raise ValueError(f"device evaluation supports <= {min(AP_MAX_PROPOSALS, _nms.MAX_K)} "
+                             f"proposals and <= {AP_MAX_GT} GT boxes per scene (got K={K}, G={G})")
         scores, _ = parse_predictions_device(predicted_box_corners, sem_cls_probs,
                                              objectness_probs, point_cloud, self.ap_config_dict)
         self._scores.append(scores)

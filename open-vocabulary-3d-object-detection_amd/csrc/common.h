@@ -21,6 +21,10 @@ __device__ __forceinline__ unsigned long long lanemask_lt() {
     return lane == 0 ? 0ull : (~0ull >> (64u - lane));
 }
 
+// host: ov3d_eval_large_kernels(1) is set (nms.hip): the K <= 2048 evaluation kernels at
+// every shape
+bool ov3d_eval_large_on();
+
 // host: reserve 2 stamp words per wave of the next launch while stamps are armed (attn.hip
 // ov3d_stamps_arm); kind 0 / 1 / 2 attention fwd / dQ / dK-dV, 3 gemm256; null when disarmed,
 // below the armed min_work, or out of space

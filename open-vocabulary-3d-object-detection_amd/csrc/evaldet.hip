@@ -244,6 +244,84 @@ __global__ void ap_match_kernel(const double* __restrict__ iou, const float* __r
     }
 }
 
+// The same walk for K <= 2048 and G <= 1024, one workgroup per (scene, class), without the
+// serial selection scan.  The walk's outcome has a closed form: a detection's GT (first GT of
+// the class with the largest IoU, scanned exactly as above) does not depend on the other
+// detections, and a GT is marked by the first detection in confidence order that hits it.  So
+//   rank_k  = detections of the class before k (higher score; ties: lower box index),
+//   j_k     = k's GT if its IoU > thresh, else none,
+//   first_j = min rank_k over the detections with j_k = j   (atomicMin in LDS),
+//   tp_k    = (j_k is some j and first_j == rank_k).
+// A detection is a score > -inf (NaN is none), as the scan above takes them.
+constexpr int kMatchMaxK = 2048;
+constexpr int kMatchMaxG = 1024;
+constexpr int kMatchThreads = 256;
+
+__global__ __launch_bounds__(kMatchThreads) void ap_match_big_kernel(
+    const double* __restrict__ iou, const float* __restrict__ scores,
+    const int64_t* __restrict__ gt_cls, const uint8_t* __restrict__ gvalid, int K, int G, int C,
+    double thresh, uint8_t* __restrict__ tp) {
+    __shared__ float s_sc[kMatchMaxK];             // the class's scores, -inf = no detection
+    __shared__ unsigned short s_gl[kMatchMaxG];    // the class's GT boxes, ascending
+    __shared__ int s_first[kMatchMaxG];            // per listed GT: rank of its first hit
+    __shared__ int s_m;
+    const int s = blockIdx.x / C, c = blockIdx.x % C;
+    const int tid = threadIdx.x;
+    const float* sc = scores + (long long)s * K * C + c;
+    for (int k = tid; k < K; k += kMatchThreads) {
+        const float v = sc[(long long)k * C];
+        s_sc[k] = v > -INFINITY ? v : -INFINITY;
+    }
+    if (tid < 64) {   // wave 0: ordered list of the class's GT boxes
+        int m = 0;
+        for (int g0 = 0; g0 < G; g0 += 64) {
+            const int g = g0 + tid;
+            const bool is = g < G && gvalid[(long long)s * G + g] && gt_cls[(long long)s * G + g] == c;
+            const unsigned long long bal = __ballot(is);
+            if (is) s_gl[m + __popcll(bal & lanemask_lt())] = (unsigned short)g;
+            m += __popcll(bal);
+        }
+        if (tid == 0) s_m = m;
+    }
+    for (int q = tid; q < G; q += kMatchThreads) s_first[q] = 0x7fffffff;
+    __syncthreads();
+    const int m = s_m;
+    int rank[kMatchMaxK / kMatchThreads], jm[kMatchMaxK / kMatchThreads];
+#pragma unroll
+    for (int u = 0; u < kMatchMaxK / kMatchThreads; ++u) {
+        const int k = u * kMatchThreads + tid;
+        rank[u] = -1;
+        jm[u] = -1;
+        if (k >= K) continue;
+        const float si = s_sc[k];
+        if (!(si > -INFINITY)) continue;
+        int r = 0;
+        for (int j = 0; j < K; ++j) {
+            const float sj = s_sc[j];
+            r += (sj > si) || (sj == si && j < k);
+        }
+        rank[u] = r;
+        const double* row = iou + ((long long)s * K + k) * G;
+        double ovmax = -INFINITY;
+        int jmax = -1;
+        for (int q = 0; q < m; ++q) {
+            const double v = row[s_gl[q]];
+            if (v > ovmax) { ovmax = v; jmax = q; }
+        }
+        if (jmax >= 0 && ovmax > thresh) {
+            jm[u] = jmax;
+            atomicMin(&s_first[jmax], r);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kMatchMaxK / kMatchThreads; ++u) {
+        const int k = u * kMatchThreads + tid;
+        if (rank[u] < 0) continue;
+        tp[((long long)s * K + k) * C + c] = (jm[u] >= 0 && s_first[jm[u]] == rank[u]) ? 1 : 0;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // voc_ap per class (one workgroup each) from TP flags in global descending-score order:
 //   prec_d = tp_d / (d + 1), rec_d = tp_d / npos; the area under the precision envelope
@@ -327,13 +405,19 @@ extern "C" int ov3d_box3d_iou_eval(const float* pred, const uint8_t* pvalid, con
 extern "C" int ov3d_ap_match(const double* iou, const float* scores, const int64_t* gt_cls,
                              const uint8_t* gvalid, int S, int K, int G, int C, double thresh,
                              uint8_t* tp, void* stream) {
-    if (!iou || !scores || !gt_cls || !gvalid || !tp || S < 0 || K < 0 || K > 256 || G < 0 ||
-        G > 64 || C <= 0)
+    if (!iou || !scores || !gt_cls || !gvalid || !tp || S < 0 || K < 0 || K > kMatchMaxK || G < 0 ||
+        G > kMatchMaxG || C <= 0)
         return OV3D_EINVAL;
     const long long n = (long long)S * C;
     if (n == 0 || K == 0) return OV3D_OK;
-    hipLaunchKernelGGL(ap_match_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0,
-                       ov3d_stream(stream), iou, scores, gt_cls, gvalid, S, K, G, C, thresh, tp);
+    if (K > 256 || G > 64 || ov3d_eval_large_on()) {
+        if (n > 0x7fffffffll) return OV3D_EINVAL;
+        hipLaunchKernelGGL(ap_match_big_kernel, dim3((unsigned)n), dim3(kMatchThreads), 0,
+                           ov3d_stream(stream), iou, scores, gt_cls, gvalid, K, G, C, thresh, tp);
+    } else {
+        hipLaunchKernelGGL(ap_match_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0,
+                           ov3d_stream(stream), iou, scores, gt_cls, gvalid, S, K, G, C, thresh, tp);
+    }
     OV3D_LAUNCH_CHECK();
     return OV3D_OK;
 }

@@ -3,17 +3,28 @@
 * ``nms_3d_faster_samecls(boxes, overlap_threshold, old_type=False)`` and
   ``nms_3d_faster(...)``: same signature and return value (pick list, in pick
   order) as the reference numpy functions for one scene;
+* ``nms_2d_faster(boxes, overlap_threshold, old_type=False)``: the reference's 2D NMS
+  (utils/nms.py:43-76) on the same kernel, each row lifted to a box of unit depth;
 * ``nms3d_batched``: all scenes of a batch in one launch, straight from device
   tensors -> (B, K) keep mask, the ``pred_mask`` of ap_calculator.py:153-190.
 Float64 arithmetic in the reference's evaluation order; score ties break
 towards the larger index (np.argsort(kind="stable") read from the back).
+Up to ``MAX_K`` = 2048 boxes per scene (the encoders emit at most 2048 points, and the
+queries are a subset of them); ``large_kernels(1)`` runs the kernels for the large shapes
+at every shape.
 """
 import numpy as np
 import torch
 
 from . import _native as nat
 
-MAX_K = 512
+MAX_K = 2048
+
+
+def large_kernels(on=-1):
+    """ov3d_eval_large_kernels: 1 = ov3d_nms3d and ov3d_ap_match use their large-shape kernels
+    at every shape, 0 = dispatch on the shape (default), -1 = only query.  -> previous setting."""
+    return int(nat.load().ov3d_eval_large_kernels(int(on)))
 
 
 def nms3d_batched(boxes, overlap_threshold, old_type=False, samecls=True, valid=None):
@@ -46,9 +57,24 @@ def nms_boxes_from_corners(corners, obj_prob, sem_cls=None):
     return out
 
 
-def _single(boxes, thr, old_type, samecls):
+def boxes2d_as_3d(boxes2d):
+    """(..., >=5) rows (x1, y1, x2, y2, score) -> (..., 7) rows [x1, 0, y1, x2, 1, y2, score]:
+    the product with the unit extent is exact, so volume = area and intersection = w * h"""
+    out = boxes2d.new_zeros(boxes2d.shape[:-1] + (7,))
+    out[..., 0] = boxes2d[..., 0]
+    out[..., 2] = boxes2d[..., 1]
+    out[..., 3] = boxes2d[..., 2]
+    out[..., 4] = 1.0
+    out[..., 5] = boxes2d[..., 3]
+    out[..., 6] = boxes2d[..., 4]
+    return out
+
+
+def _single(boxes, thr, old_type, samecls, two_d=False):
     dev = torch.device("cuda", torch.cuda.current_device())
     b = torch.as_tensor(np.ascontiguousarray(boxes, dtype=np.float64), device=dev)[None]
+    if two_d:
+        b = boxes2d_as_3d(b)
     keep = nms3d_batched(b, thr, old_type=old_type, samecls=samecls)[0]
     score = b[0, :, 6]
     idx = torch.nonzero(keep).flatten()
@@ -63,3 +89,7 @@ def nms_3d_faster(boxes, overlap_threshold, old_type=False):
 
 def nms_3d_faster_samecls(boxes, overlap_threshold, old_type=False):
     return _single(boxes, overlap_threshold, old_type, samecls=True)
+
+
+def nms_2d_faster(boxes, overlap_threshold, old_type=False):
+    return _single(boxes, overlap_threshold, old_type, samecls=False, two_d=True)

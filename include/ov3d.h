@@ -1132,7 +1132,17 @@ int ov3d_rows_gather(const void* feat, long long rows_per_scene, long long row_b
  *   ov3d_box_points_count: remove_empty_box (ap_calculator.py:70-84): for every predicted box
  *     (corners (B,K,8,3) f32, upright camera, flipped to depth as flip_axis_to_depth), the
  *     number of scene points inside its convex hull (in_hull, box_util.py:22-31);
- *     point (b, n) xyz at pts[b*pt_sb + n*pt_sn + 0..2] -> counts (B,K) int32
+ *     point (b, n) xyz at pts[b*pt_sb + n*pt_sn + 0..2] -> counts (B,K) int32.  That is
+ *     kind 0: pts f32 (pt_f64 0), labels NULL, C 0, mode NULL.
+ *     kind 1, the label vote of pseudo-label generation (utils/label_formatter.py:155-158
+ *     gen_pseudo, :183-188 crop_pc): boxes (B,K,6) f32 = lower xyz, upper xyz, axis-aligned;
+ *     a point is inside iff lo <= p <= hi on every axis, compared in the point's own type
+ *     (pt_f64 1: pts f64, the f32 bound widened; strides in elements of that type); NaN is
+ *     never inside, lo > hi is an empty box.  labels (B,N) u8: a value < C votes for that
+ *     class, any other does not vote (255 pads a row).  1 <= C <= 32; B, K, N >= 1.
+ *     -> counts (B,K,C) int32, written in full, and mode (B,K) int32 (may be NULL): the
+ *     smallest label among the most frequent (scipy.stats.mode), -1 when no vote is inside.
+ *     Any other combination is OV3D_EINVAL before any launch.
  *   ov3d_box3d_iou_eval: box3d_iou (box_util.py:116-141) of every (prediction, GT) pair of a
  *     scene: pred (S,K,8,3) f32 with pvalid (S,K) u8, gt (S,G,8,3) f32 with gvalid (S,G) u8
  *     -> iou (S,K,G) f64 (0 where either is invalid)
@@ -1144,8 +1154,9 @@ int ov3d_rows_gather(const void* feat, long long rows_per_scene, long long row_b
  *     in global descending-confidence order, tp_sorted (C, M) u8 with nvalid (C) leading
  *     entries valid, npos (C) GT counts; tp_pos (C, tp_cap) int32 workspace
  *     -> ap (C) f64, rec_last (C) f64 (the recall at the last detection) */
-int ov3d_box_points_count(const float* pts, long long pt_sb, long long pt_sn, int N,
-                          const float* corners, int B, int K, int32_t* counts, void* stream);
+int ov3d_box_points_count(const void* pts, int pt_f64, long long pt_sb, long long pt_sn, int N,
+                          const float* boxes, int kind, const uint8_t* labels, int C,
+                          int B, int K, int32_t* counts, int32_t* mode, void* stream);
 int ov3d_box3d_iou_eval(const float* pred, const uint8_t* pvalid, const float* gt,
                         const uint8_t* gvalid, int S, int K, int G, double* iou, void* stream);
 int ov3d_ap_match(const double* iou, const float* scores, const int64_t* gt_cls,

@@ -9,6 +9,7 @@ Drop-in modules (reference module -> here):
   utils.nms                               -> nms               (batched NMS on HIP)
   utils.dist                              -> dist              (RCCL over xGMI)
   models.model_regionclip (RegionCLIP)    -> regionclip        (ROIAlign on HIP, res5 + pool batched)
+  utils.label_formatter (LabelFormatter)  -> label_formatter   (pseudo-label box vote on HIP)
 The HIP kernels live in lib/libov3d_hip.so (C ABI: include/ov3d.h); there is
 no CPU fallback.
 """

@@ -57,8 +57,8 @@ def box_points_count(point_cloud, corners):
     c = nat.check(corners.detach().float().contiguous(), "corners", torch.float32, 4)
     B, K = c.shape[:2]
     out = torch.empty((B, K), dtype=torch.int32, device=c.device)
-    nat.call("ov3d_box_points_count", pc, pc.stride(0), pc.stride(1), pc.shape[1], c, B, K, out,
-             like=c)
+    nat.call("ov3d_box_points_count", pc, 0, pc.stride(0), pc.stride(1), pc.shape[1], c, 0, None, 0,
+             B, K, out, None, like=c)
     return out
 
 

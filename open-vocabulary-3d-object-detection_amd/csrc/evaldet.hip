@@ -3,7 +3,9 @@
 // Replaces the CPU evaluation of utils/ap_calculator.py and utils/eval_det.py:
 //   ov3d_box_points_count : remove_empty_box (ap_calculator.py:70-84) — points of the scene
 //                           inside each predicted box's convex hull (box_util.py:22-31,
-//                           scipy Delaunay.find_simplex), after flip_axis_to_depth
+//                           scipy Delaunay.find_simplex), after flip_axis_to_depth; kind 1:
+//                           the label vote of pseudo-label generation
+//                           (utils/label_formatter.py gen_pseudo) over axis-aligned boxes
 //   ov3d_box3d_iou_eval   : box3d_iou (box_util.py:116-141) of every (prediction, GT) pair
 //                           of a scene: Sutherland-Hodgman clip of the bird's-eye rectangles
 //                           (polygon_clip, box_util.py:34-80) in double, the Python
@@ -114,6 +116,76 @@ __global__ __launch_bounds__(kCountThreads) void box_points_count_kernel(
     __syncthreads();
     if (threadIdx.x < kBoxesPerWG && k0 + (int)threadIdx.x < K)
         counts[(long long)b * K + k0 + threadIdx.x] = s_cnt[threadIdx.x];
+}
+
+// ---------------------------------------------------------------------------
+// label vote (utils/label_formatter.py:155-158 gen_pseudo, :183-188 crop_pc): per axis-aligned
+// box (lo xyz, hi xyz; closed intervals) the histogram of the per-vertex labels inside it and
+// scipy.stats.mode's answer, the smallest label among the most frequent.  T is the points' own
+// type: numpy compares a float32 point with the float32 bound, a float64 point with the bound
+// widened to double.  Same layout as the hull count: 8 boxes per workgroup, every point of the
+// scene once per workgroup; hits are sparse, so they go straight into an 8 x 32 LDS histogram.
+// Labels are read 4 at a time from the first 4-byte-aligned address of the scene's row.
+constexpr int kVoteThreads = 1024;
+constexpr int kVoteMaxC = 32;
+
+template <typename T>
+__device__ __forceinline__ void vote_point(const T* __restrict__ p, unsigned label, int C,
+                                           const T (*s_b)[6], int (*s_hist)[kVoteMaxC]) {
+    if (label >= (unsigned)C) return;
+    const T x = p[0], y = p[1], z = p[2];
+#pragma unroll
+    for (int q = 0; q < kBoxesPerWG; ++q) {
+        // NaN compares false: never inside; lo > hi: nothing inside
+        if (x >= s_b[q][0] && y >= s_b[q][1] && z >= s_b[q][2] && x <= s_b[q][3] &&
+            y <= s_b[q][4] && z <= s_b[q][5])
+            atomicAdd(&s_hist[q][label], 1);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kVoteThreads) void box_label_vote_kernel(
+    const T* __restrict__ pts, long long pt_sb, long long pt_sn, int N,
+    const float* __restrict__ boxes, const uint8_t* __restrict__ labels, int C, int K,
+    int32_t* __restrict__ counts, int32_t* __restrict__ mode) {
+    const int b = blockIdx.y;
+    const int k0 = blockIdx.x * kBoxesPerWG;
+    __shared__ T s_b[kBoxesPerWG][6];
+    __shared__ int s_hist[kBoxesPerWG][kVoteMaxC];
+    if (threadIdx.x < kBoxesPerWG * kVoteMaxC) (&s_hist[0][0])[threadIdx.x] = 0;
+    if (threadIdx.x < kBoxesPerWG * 6) {
+        const int q = threadIdx.x / 6, a = threadIdx.x % 6;
+        // a box past K is empty (lo > hi)
+        s_b[q][a] = k0 + q < K ? (T)boxes[((long long)b * K + k0 + q) * 6 + a] : (T)(a < 3 ? 1 : 0);
+    }
+    __syncthreads();
+    const T* P0 = pts + (long long)b * pt_sb;
+    const uint8_t* L0 = labels + (long long)b * N;
+    const int head = min(N, (int)((4 - ((uintptr_t)L0 & 3)) & 3));
+    const int groups = (N - head) / 4;
+    for (int i = threadIdx.x; i < head; i += kVoteThreads)
+        vote_point<T>(P0 + (long long)i * pt_sn, L0[i], C, s_b, s_hist);
+    const uint32_t* L4 = reinterpret_cast<const uint32_t*>(L0 + head);
+#pragma unroll 2
+    for (int g = threadIdx.x; g < groups; g += kVoteThreads) {
+        const uint32_t l4 = L4[g];
+        const T* p = P0 + (long long)(head + 4 * g) * pt_sn;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) vote_point<T>(p + j * pt_sn, (l4 >> (8 * j)) & 0xffu, C, s_b, s_hist);
+    }
+    for (int i = head + 4 * groups + threadIdx.x; i < N; i += kVoteThreads)
+        vote_point<T>(P0 + (long long)i * pt_sn, L0[i], C, s_b, s_hist);
+    __syncthreads();
+    for (int e = threadIdx.x; e < kBoxesPerWG * C; e += kVoteThreads) {
+        const int q = e / C, c = e % C;
+        if (k0 + q < K) counts[((long long)b * K + k0 + q) * C + c] = s_hist[q][c];
+    }
+    if (mode && threadIdx.x < kBoxesPerWG && k0 + (int)threadIdx.x < K) {
+        int best = -1, most = 0;
+        for (int c = 0; c < C; ++c)
+            if (s_hist[threadIdx.x][c] > most) { most = s_hist[threadIdx.x][c]; best = c; }
+        mode[(long long)b * K + k0 + threadIdx.x] = best;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -378,14 +450,33 @@ __global__ __launch_bounds__(kCurveThreads) void ap_curve_kernel(
 
 }  // namespace
 
-extern "C" int ov3d_box_points_count(const float* pts, long long pt_sb, long long pt_sn, int N,
-                                     const float* corners, int B, int K, int32_t* counts,
+extern "C" int ov3d_box_points_count(const void* pts, int pt_f64, long long pt_sb, long long pt_sn,
+                                     int N, const float* boxes, int kind, const uint8_t* labels,
+                                     int C, int B, int K, int32_t* counts, int32_t* mode,
                                      void* stream) {
-    if (!pts || !corners || !counts || B < 0 || K < 0 || N < 0 || pt_sn < 3) return OV3D_EINVAL;
-    if (B == 0 || K == 0) return OV3D_OK;
-    hipLaunchKernelGGL(box_points_count_kernel, dim3((K + kBoxesPerWG - 1) / kBoxesPerWG, B),
-                       dim3(kCountThreads), 0, ov3d_stream(stream), pts, pt_sb, pt_sn, N, corners,
-                       K, counts);
+    if (!pts || !boxes || !counts || pt_sn < 3 || B < 0 || K < 0 || N < 0) return OV3D_EINVAL;
+    const dim3 grid((K + kBoxesPerWG - 1) / kBoxesPerWG, B);
+    if (kind == 0) {
+        if (pt_f64 != 0 || labels || C != 0 || mode) return OV3D_EINVAL;
+        if (B == 0 || K == 0) return OV3D_OK;
+        hipLaunchKernelGGL(box_points_count_kernel, grid, dim3(kCountThreads), 0,
+                           ov3d_stream(stream), static_cast<const float*>(pts), pt_sb, pt_sn, N,
+                           boxes, K, counts);
+    } else if (kind == 1) {
+        if ((pt_f64 != 0 && pt_f64 != 1) || !labels || C < 1 || C > kVoteMaxC || B < 1 ||
+            B > 65535 || K < 1 || N < 1)
+            return OV3D_EINVAL;
+        if (pt_f64)
+            hipLaunchKernelGGL(box_label_vote_kernel<double>, grid, dim3(kVoteThreads), 0,
+                               ov3d_stream(stream), static_cast<const double*>(pts), pt_sb, pt_sn,
+                               N, boxes, labels, C, K, counts, mode);
+        else
+            hipLaunchKernelGGL(box_label_vote_kernel<float>, grid, dim3(kVoteThreads), 0,
+                               ov3d_stream(stream), static_cast<const float*>(pts), pt_sb, pt_sn,
+                               N, boxes, labels, C, K, counts, mode);
+    } else {
+        return OV3D_EINVAL;
+    }
     OV3D_LAUNCH_CHECK();
     return OV3D_OK;
 }

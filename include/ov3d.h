@@ -1175,6 +1175,9 @@ int ov3d_stamps_count(void);
 int ov3d_stamps_get(int i, int* kind, long long* word_off, long long* waves, long long* work);
 long long ov3d_wall_clock_khz(void);
 
+/* The pseudo-box lifting entries of the same library (csrc/lift.hip: ov3d_lift_frustum,
+ * ov3d_lift_image, ov3d_lift_nms, ov3d_lift_match) are declared in include/ov3d_lift.h. */
+
 #ifdef __cplusplus
 }
 #endif

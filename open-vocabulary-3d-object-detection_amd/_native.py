@@ -86,6 +86,19 @@ def _read_own_header():
 
 _STRUCT_FIELDS, _PROTOS = _read_own_header()
 EXPORTS = tuple(_PROTOS)
+
+
+def _read_lift_header():
+    """the lifting entries (include/ov3d_lift.h, csrc/lift.hip), read the same way"""
+    if not os.path.exists(LIFT_HEADER_PATH):
+        raise NativeError(f"{LIFT_HEADER_PATH} not found: the ctypes binding is derived from it")
+    with open(LIFT_HEADER_PATH) as f:
+        return read_header(f.read())[1]
+
+
+LIFT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_lift.h")
+_LIFT_PROTOS = _read_lift_header()
+LIFT_EXPORTS = tuple(_LIFT_PROTOS)
 _STRUCTS = {}
 
 
@@ -105,7 +118,7 @@ def load():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU fallback); "
                 "build it with `make -C open-vocabulary-3d-object-detection_amd/csrc`")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _PROTOS.items():
+        for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -1176,7 +1176,9 @@ int ov3d_stamps_get(int i, int* kind, long long* word_off, long long* waves, lon
 long long ov3d_wall_clock_khz(void);
 
 /* The pseudo-box lifting entries of the same library (csrc/lift.hip: ov3d_lift_frustum,
- * ov3d_lift_image, ov3d_lift_nms, ov3d_lift_match) are declared in include/ov3d_lift.h. */
+ * ov3d_lift_image, ov3d_lift_nms, ov3d_lift_match) are declared in include/ov3d_lift.h, the
+ * box evaluation entries (csrc/boxeval.hip: ov3d_boxeval_match, ov3d_boxeval_tally) in
+ * include/ov3d_boxeval.h. */
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,9 @@ Drop-in modules (reference module -> here):
   utils.dist                              -> dist              (RCCL over xGMI)
   models.model_regionclip (RegionCLIP)    -> regionclip        (ROIAlign on HIP, res5 + pool batched)
   utils.label_formatter (LabelFormatter)  -> label_formatter   (pseudo-label box vote on HIP)
+  3DOVDet_tools scannet/lift_boxes.py     -> lift_boxes        (frustum lift, NMS, pool match on HIP)
+  3DOVDet_tools scannet/evaluate_box.py,
+    utils.evaluation.pr_helper.PRCalculator -> box_eval        (precision / recall of a split on HIP)
 The HIP kernels live in lib/libov3d_hip.so (C ABI: include/ov3d.h); there is
 no CPU fallback.
 """

@@ -99,6 +99,19 @@ def _read_lift_header():
 LIFT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_lift.h")
 _LIFT_PROTOS = _read_lift_header()
 LIFT_EXPORTS = tuple(_LIFT_PROTOS)
+
+
+def _read_boxeval_header():
+    """the box evaluation entries (include/ov3d_boxeval.h, csrc/boxeval.hip), read the same way"""
+    if not os.path.exists(BOXEVAL_HEADER_PATH):
+        raise NativeError(f"{BOXEVAL_HEADER_PATH} not found: the ctypes binding is derived from it")
+    with open(BOXEVAL_HEADER_PATH) as f:
+        return read_header(f.read())[1]
+
+
+BOXEVAL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_boxeval.h")
+_BOXEVAL_PROTOS = _read_boxeval_header()
+BOXEVAL_EXPORTS = tuple(_BOXEVAL_PROTOS)
 _STRUCTS = {}
 
 
@@ -118,7 +131,7 @@ def load():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU fallback); "
                 "build it with `make -C open-vocabulary-3d-object-detection_amd/csrc`")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS}.items():
+        for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS, **_BOXEVAL_PROTOS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -112,6 +112,19 @@ def _read_boxeval_header():
 BOXEVAL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_boxeval.h")
 _BOXEVAL_PROTOS = _read_boxeval_header()
 BOXEVAL_EXPORTS = tuple(_BOXEVAL_PROTOS)
+
+
+def _read_backproj_header():
+    """the back-projection entries (include/ov3d_backproj.h, csrc/backproj.hip), read the same way"""
+    if not os.path.exists(BACKPROJ_HEADER_PATH):
+        raise NativeError(f"{BACKPROJ_HEADER_PATH} not found: the ctypes binding is derived from it")
+    with open(BACKPROJ_HEADER_PATH) as f:
+        return read_header(f.read())[1]
+
+
+BACKPROJ_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_backproj.h")
+_BACKPROJ_PROTOS = _read_backproj_header()
+BACKPROJ_EXPORTS = tuple(_BACKPROJ_PROTOS)
 _STRUCTS = {}
 
 
@@ -131,7 +144,8 @@ def load():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU fallback); "
                 "build it with `make -C open-vocabulary-3d-object-detection_amd/csrc`")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS, **_BOXEVAL_PROTOS}.items():
+        for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS, **_BOXEVAL_PROTOS,
+                                           **_BACKPROJ_PROTOS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype

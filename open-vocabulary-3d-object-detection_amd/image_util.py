@@ -6,8 +6,31 @@ Reference quirk Q4 reproduced: the predicted *full* size is used as the
 half-extent (image_util.py:124-127 receives size_unnormalized), and the box is
 returned as [min v, min u, max v, max u] (x/y swapped, image_util.py:131-133)
 before the [w, h, w, h] clamp of criterion.py:389-391.
+
+``image_processor`` (image_util.py:17,65) is the multiview side: its ``compute_projection``
+matches every scan vertex to a pixel of every frame's 41 x 32 feature map, all frames in three
+launches (ov3d_amd.projection, csrc/backproj.hip).  The frame file decoding of the reference
+class (``load_image``, ``load_depth``, ``resize_crop_image``: imageio, torchvision) is not here.
 """
 import torch
+
+from .projection import INTRINSICS, ProjectionHelper  # noqa: F401
+
+
+class image_processor:
+    def __init__(self):
+        self.PROJECTOR = ProjectionHelper(INTRINSICS, 0.1, 4.0, [41, 32], 0.05)
+
+    def to_tensor(self, arr):
+        """float32 on the device (float64 input is cast first, as torch.Tensor(arr) does)"""
+        return torch.as_tensor(arr).to(dtype=torch.float32).cuda()
+
+    def compute_projection(self, points, depth, camera_to_world):
+        """points (N,3), depth (F,32,41), camera_to_world (F,4,4), numpy or torch, host or device
+        -> (indices_3d, indices_2d), each (F, N+1) int64 on the device: per frame the number of
+        mapped points, then their indices ascending / their pixel indices, then zeros.  A frame
+        that maps nothing keeps an all-zero row.  No synchronisation and no print."""
+        return self.PROJECTOR.compute_projections(points, depth, camera_to_world)
 
 
 class Boxes:

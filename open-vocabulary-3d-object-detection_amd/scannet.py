@@ -18,7 +18,8 @@ There is no RandomCuboid (commented out in the reference, :309-317: ``use_random
 before the first launch and ``get_batch`` never reads anything back from the device.
 
 Scope: ``use_image`` (the multiview frame loader; needs imageio and torchvision) and
-``use_height`` (never passed by build_dataset) raise NotImplementedError.  ``use_pbox`` reads the
+``use_height`` (never passed by build_dataset) raise NotImplementedError; the per-vertex
+features themselves come from ``ov3d_amd.projection.compose_features``.  ``use_pbox`` reads the
 boxes from ``pseudo_box_dir`` instead (scannet.py:264-267).  ``pcl_color`` holds the raw colours,
 or with ``use_color`` the normalised ones (in the reference it is a view of the normalised array).
 

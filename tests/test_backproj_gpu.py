@@ -1,0 +1,392 @@
+"""Multiview back-projection on the GPU (csrc/backproj.hip behind include/ov3d_backproj.h): every
+entry against the numpy restatement (tests/backproj_ref.py), bit for bit, at the shapes where the
+tiling can go wrong (one point, around a wave, around the 1024-point block, several blocks; one
+frame, fewer frames than waves, more); the edge frames; the public methods end to end against
+the reference's recorded results (tests/golden/backproj.npz); compose_features against its
+loop definition; both inside a hipGraph capture (a synchronisation raises there); the guard-band
+cases (tests/guard.py) of the four entries; and the composed rows as a training batch's
+feature_2d."""
+import numpy as np
+import pytest
+import torch
+
+import backproj_cases as BC
+import backproj_ref as R
+import guard
+from guard import In, Out
+from helpers import ov3d  # noqa: F401
+from lift_cases import look_at
+from test_backproj_cpu import PAR, gold, same
+
+pytestmark = pytest.mark.gpu
+
+NS = (1, 63, 64, 65, 1023, 1024, 1025, 2500)
+FS = (1, 2, 5, 17)
+W, H = BC.IMAGE_DIMS
+
+
+def dev(a, cuda):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def scene(N, F, seed=0, C=3):
+    """N vertices of the room, F frames from random eyes inside it looking at a random vertex"""
+    rng = np.random.Generator(np.random.PCG64(1000 * N + 10 * F + seed))
+    pts = BC.draw_points(rng, N)
+    poses = np.stack([look_at(rng.uniform([0.4, 0.4, 1.0], [4.6, 3.6, 2.0]),
+                              pts[rng.integers(0, N)].astype(np.float64) + rng.normal(0, 0.01, 3))
+                      for _ in range(F)])
+    depth = np.stack([BC.ray_cast(P, PAR) for P in poses])
+    depth[rng.random(depth.shape) < 0.03] = 0.0
+    feats = (rng.integers(-128, 128, (F, C, H, W)) / 16.0).astype(np.float32)
+    return pts, depth, poses, feats
+
+
+@pytest.fixture(scope="module")
+def refs():
+    out = {}
+    for N in NS:
+        for F in FS:
+            case = scene(N, F)
+            i3, i2 = R.tables(*case[:3], PAR)
+            out[N, F] = (case, R.frame_table(case[2], PAR), i3, i2, R.compose_loop(case[3], i3, i2, N))
+    return out
+
+
+@pytest.fixture(scope="module")
+def helper(ov3d):
+    from ov3d_amd import image_util
+    return image_util.image_processor().PROJECTOR
+
+
+# ---------------------------------------------------------------- every entry, every shape
+
+@pytest.mark.parametrize("N", NS)
+def test_entries_equal_the_restatement(cuda, helper, refs, N):
+    from ov3d_amd import projection
+    mapped = 0
+    for F in FS:
+        (pts, depth, poses, feats), table, i3, i2, (comp, frame) = refs[N, F]
+        d = [dev(x, cuda) for x in (pts, depth, poses, feats)]
+        assert same(host(helper.frame_table(d[2])), table), (N, F)
+        g3, g2 = helper.compute_projections(*d[:3])
+        assert same(host(g3), i3) and same(host(g2), i2), (N, F)
+        for f in (0, F - 1):
+            assert same(host(helper.project(d[3][f], g3[f], g2[f], N)), R.project(feats[f], i3[f], i2[f], N)), (N, F, f)
+        out, fr = projection.compose_features(*d)
+        assert same(host(out), comp) and same(host(fr), frame), (N, F)
+        out, fr = projection.compose_features(*d, rows=True)
+        assert same(host(out), np.ascontiguousarray(comp.T)) and same(host(fr), frame), (N, F)
+        mapped += int(i3[:, 0].sum())
+    if N >= 63:
+        assert mapped > 0
+
+
+def test_a_depth_map_too_large_for_lds(cuda, ov3d):
+    """128 x 80 pixels: the tables kernels read the depth map from global memory"""
+    from ov3d_amd import projection
+    dims = (128, 80)
+    intr = [[115.0, 0, 63.5, 0], [0, 115.0, 39.5, 0], [0, 0, 1, 0], [0, 0, 0, 1]]
+    hp = projection.ProjectionHelper(intr, 0.1, 4.0, list(dims), 0.05)
+    par = R.params(intr, 0.1, 4.0, dims, 0.05)
+    assert same(hp.host_params().numpy(), par)
+    rng = np.random.Generator(np.random.PCG64(5))
+    pts = BC.draw_points(rng, 1500)
+    poses = np.stack([look_at((0.8, 0.7, 1.5), (3.5, 3.0, 0.6)), look_at((2.0, 3.5, 1.4), (2.0, 1.5, 0.8))])
+    depth = np.stack([BC.ray_cast(P, par, dims) for P in poses])
+    feats = (rng.integers(-128, 128, (2, 2, dims[1], dims[0])) / 16.0).astype(np.float32)
+    i3, i2 = R.tables(pts, depth, poses, par, dims)
+    assert i3[:, 0].min() > 50
+    g3, g2 = hp.compute_projections(pts, depth, poses)
+    assert same(host(g3), i3) and same(host(g2), i2)
+    comp, frame = R.compose_loop(feats, i3, i2, len(pts))
+    out, fr = projection.compose_features(pts, depth, poses, feats, projector=hp)
+    assert same(host(out), comp) and same(host(fr), frame)
+
+
+# ---------------------------------------------------------------- edge frames
+
+def edge_scene():
+    """frames: 0 looks away; 1 sees every vertex of its own block (vertices 0..199 sit on its
+    pixels' rays at the map's depth); 2 a -inf pose; 3 a singular finite pose; 4 frame 1's pose
+    with an all-zero depth map; 5 the identity pose in front of a flat wall, with vertices on
+    pixel boundaries and NaN vertices"""
+    rng = np.random.Generator(np.random.PCG64(77))
+    P1 = look_at((0.8, 0.7, 1.5), (3.5, 3.0, 0.6))
+    poses = np.stack([look_at((-1.0, 2.0, 1.3), (-4.0, 2.1, 1.2)), P1, np.full((4, 4), -np.inf, np.float32),
+                      np.diag([1.0, 1.0, 0.0, 1.0]).astype(np.float32), P1, np.eye(4, dtype=np.float32)])
+    depth = np.stack([BC.ray_cast(P, PAR) if np.isfinite(P).all() else np.zeros((H, W), np.float32) for P in poses])
+    depth[4] = 0.0
+    depth[5] = 2.0
+    u, v = rng.integers(2, W - 2, 200), rng.integers(2, H - 2, 200)
+    d = depth[1][v, u].astype(np.float64)
+    cam = np.stack([(u - 20.0) / 37.01983 * d, (v - 15.5) / 38.52470 * d, d], 1)
+    on_rays = cam @ P1[:3, :3].astype(np.float64).T + P1[:3, 3]
+    ok = (d >= 0.2) & (d <= 3.9)
+    on_rays[~ok] = on_rays[ok][0]
+    special = np.array([[(40.5 - 20.0) / 37.01983 * 2.0, 0.0, 2.0], [(10.5 - 20.0) / 37.01983 * 2.0, 0.1, 2.0],
+                        [0.0, (20.5 - 15.5) / 38.52470 * 2.0, 2.0], [0.3, 0.2, 2.0], [0.3, 0.2, 2.05],
+                        [0.3, 0.2, 2.0500002], [np.nan, 0.2, 2.0], [0.3, np.nan, np.nan], [np.inf, 0.0, 2.0]])
+    pts = np.concatenate([on_rays, BC.draw_points(rng, 300).astype(np.float64), special]).astype(np.float32)
+    feats = (rng.integers(-128, 128, (len(poses), 3, H, W)) / 16.0).astype(np.float32)
+    return pts, depth, poses, feats
+
+
+def test_edge_frames(cuda, helper):
+    from ov3d_amd import projection
+    pts, depth, poses, feats = edge_scene()
+    N = len(pts)
+    table = R.frame_table(poses, PAR)
+    i3, i2 = R.tables(pts, depth, poses, PAR)
+    # what the scene is for, on the restatement
+    assert table[:, 36].tolist() == [1, 1, 0, 0, 1, 1]
+    assert not i3[[0, 2, 3, 4]].any() and not i2[[0, 2, 3, 4]].any()
+    assert i3[1, 0] >= 200 and np.array_equal(i3[1, 1:201], np.arange(200))       # vertex 0 mapped, slot 1 holds 0
+    first_special = N - 9
+    kept5 = set(i3[5, 1:1 + i3[5, 0]].tolist())
+    assert first_special + 3 in kept5 and not kept5 & {first_special, first_special + 6, first_special + 7, first_special + 8}
+    assert same(host(helper.frame_table(poses)), table)
+    g3, g2 = helper.compute_projections(pts, depth, poses)
+    assert same(host(g3), i3) and same(host(g2), i2)
+    comp, frame = R.compose_loop(feats, i3, i2, N)
+    for rows in (False, True):
+        out, fr = projection.compose_features(pts, depth, poses, feats, rows=rows)
+        assert same(host(out), np.ascontiguousarray(comp.T) if rows else comp) and same(host(fr), frame)
+    assert helper.compute_projection(pts, depth[0], poses[0]) is None
+    assert helper.compute_projection(pts, depth[2], poses[2]) is None
+    one = helper.compute_projection(pts, depth[1], poses[1])
+    assert same(host(one[0]), i3[1]) and same(host(one[1]), i2[1])
+    # every vertex of a cloud maps: the padding is empty and the last slot is used
+    j3, j2 = helper.compute_projections(pts[:200], depth[1:2], poses[1:2])
+    full3, full2 = i3[1:2, :201].copy(), i2[1:2, :201].copy()
+    full3[0, 0] = full2[0, 0] = 200
+    assert same(host(j3), full3) and same(host(j2), full2)
+
+
+# ---------------------------------------------------------------- public methods, recorded results
+
+@pytest.mark.parametrize("name", BC.CASES)
+def test_public_methods_equal_the_recorded_results(cuda, ov3d, name):
+    from ov3d_amd import image_util
+    g = gold(name)
+    proc = image_util.image_processor()
+    N, F = len(g["points"]), len(g["poses"])
+    want3, want2 = g["idx3d"].astype(np.int64), g["idx2d"].astype(np.int64)
+    inputs = {"numpy": (g["points"], g["depth"], g["poses"]),
+              "float64": (g["points"].astype(np.float64), g["depth"].astype(np.float64), g["poses"].astype(np.float64)),
+              "device": tuple(dev(g[k], cuda) for k in ("points", "depth", "poses")),
+              "host tensors": tuple(torch.from_numpy(g[k]) for k in ("points", "depth", "poses"))}
+    for kind, args in inputs.items():
+        i3, i2 = proc.compute_projection(*args)
+        assert i3.is_cuda and i3.dtype == torch.int64 and tuple(i3.shape) == (F, N + 1), kind
+        assert same(host(i3), want3) and same(host(i2), want2), kind
+    assert proc.to_tensor(g["points"].astype(np.float64)).dtype == torch.float32
+    for f in range(F):
+        one = proc.PROJECTOR.compute_projection(g["points"], g["depth"][f], g["poses"][f])
+        if want3[f, 0] == 0:
+            assert one is None, f
+            continue
+        assert same(host(one[0]), want3[f]) and same(host(one[1]), want2[f]), f
+        p = proc.PROJECTOR.project(dev(g["features"][f], cuda), one[0], one[1], N)
+        assert same(host(p), g["projected"][f]), f
+        p1 = proc.PROJECTOR.project(g["features"][f][0], one[0], one[1], N)         # 2-D label: C = 1
+        assert same(host(p1), g["projected"][f][:1]), f
+    if name == "edges":
+        assert (want3[:2, 0] == 0).all()
+
+
+# ---------------------------------------------------------------- compose_features
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [1, 3, 128])
+def test_compose_equals_the_loop_definition(cuda, ov3d, C, dtype):
+    from ov3d_amd import projection
+    for name in BC.CASES:
+        g = gold(name)
+        N, F = len(g["points"]), len(g["poses"])
+        i3, i2 = g["idx3d"].astype(np.int64), g["idx2d"].astype(np.int64)
+        rng = np.random.Generator(np.random.PCG64(C))
+        feats = (rng.integers(-128, 128, (F, C, H, W)) / 16.0).astype(np.float32)      # exact in bfloat16
+        want, frame = R.compose_loop(feats, i3, i2, N)
+        if name == "edges":
+            both = np.intersect1d(i3[2, 1:1 + i3[2, 0]], i3[3, 1:1 + i3[3, 0]])
+            assert len(both) > 0 and (frame[both] >= 3).all()                           # the last one wins
+        if C == 3:
+            assert same(R.compose_loop(g["features"], i3, i2, N)[0], g["composed"])
+        f_dev = dev(feats, cuda).to(dtype)
+        for rows in (False, True):
+            out, fr = projection.compose_features(g["points"], g["depth"], g["poses"], f_dev, rows=rows)
+            assert out.dtype == dtype and tuple(out.shape) == ((N, C) if rows else (C, N))
+            got = host(out.float())
+            assert same(got, np.ascontiguousarray(want.T) if rows else want), (name, rows)
+            assert fr.dtype == torch.int32 and same(host(fr), frame), (name, rows)
+        buf = torch.full((N, C), 9.0, dtype=dtype, device=cuda)
+        out, _ = projection.compose_features(g["points"], g["depth"], g["poses"], f_dev, rows=True, out=buf)
+        assert out is buf and same(host(buf.float()), np.ascontiguousarray(want.T))
+
+
+def test_both_paths_are_capturable(cuda, ov3d):
+    """the multi-frame tables and compose_features inside a hipGraph capture: a host
+    synchronisation or a device -> host copy raises during capture"""
+    from ov3d_amd import image_util, projection
+    g = gold("main")
+    proc = image_util.image_processor()
+    N = len(g["points"])
+    d = [dev(g[k], cuda) for k in ("points", "depth", "poses", "features")]
+    rows = torch.empty((N, 3), dtype=torch.float32, device=cuda)
+    keep = {}
+
+    def work():
+        keep["i3"], keep["i2"] = proc.compute_projection(*d[:3])
+        keep["frame"] = projection.compose_features(*d, rows=True, out=rows)[1]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        work()                                             # warm-up outside the capture
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    rows.fill_(7.0)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        work()
+    keep["i3"].fill_(-1)
+    keep["i2"].fill_(-1)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert same(host(keep["i3"]), g["idx3d"].astype(np.int64)) and same(host(keep["i2"]), g["idx2d"].astype(np.int64))
+    assert same(host(rows), np.ascontiguousarray(g["composed"].T))
+    i3 = g["idx3d"].astype(np.int64)
+    assert same(host(keep["frame"]), R.compose_loop(g["features"], i3, g["idx2d"].astype(np.int64), N)[1])
+
+
+# ---------------------------------------------------------------- guard bands
+
+GUARD_SHAPES = [(1, 1), (63, 2), (65, 5), (1025, 2), (2500, 5)]
+
+
+def _inputs(N, F):
+    pts, depth, poses, feats = scene(N, F, seed=3)
+    return pts, depth, poses, feats, {"pts": In(torch.from_numpy(pts)), "depth": In(torch.from_numpy(depth)),
+                                      "poses": In(torch.from_numpy(poses)), "params": In(torch.from_numpy(PAR))}
+
+
+@pytest.mark.parametrize("F", [1, 5, 65])
+def test_guard_frames(cuda, ov3d, F):
+    poses = scene(8, F, seed=4)[2]
+    if F >= 5:
+        poses[1] = -np.inf
+        poses[3] = np.diag([1.0, 1.0, 0.0, 1.0])
+    specs = {"poses": In(torch.from_numpy(poses)), "params": In(torch.from_numpy(PAR)),
+             "table": Out((F, R.ROW), torch.float32, finite=False)}
+    out = guard.run_case(cuda, specs, lambda t: guard.call(
+        "ov3d_backproj_frames", t["poses"], F, t["params"], t["table"], like=t["poses"]))
+    assert same(host(out["table"]), R.frame_table(poses, PAR))
+
+
+@pytest.mark.parametrize("N,F", GUARD_SHAPES)
+def test_guard_tables(cuda, ov3d, N, F):
+    pts, depth, poses, _, specs = _inputs(N, F)
+    nblk = -(-N // R.BLOCK)
+    specs.update({"table": Out((F, R.ROW), torch.float32), "counts": Out((F, nblk), torch.int32),
+                  "i3": Out((F, N + 1), torch.int64), "i2": Out((F, N + 1), torch.int64)})
+    out = guard.run_case(cuda, specs, lambda t: guard.call(
+        "ov3d_backproj_tables", t["pts"], N, t["depth"], t["poses"], F, t["params"], W, H, t["table"],
+        t["counts"], t["i3"], t["i2"], like=t["pts"]))
+    i3, i2 = R.tables(pts, depth, poses, PAR)
+    assert same(host(out["i3"]), i3) and same(host(out["i2"]), i2)
+    assert np.array_equal(host(out["counts"]).sum(1), i3[:, 0])
+
+
+@pytest.mark.parametrize("bf16", [0, 1], ids=["f32", "bf16"])
+@pytest.mark.parametrize("N,F", GUARD_SHAPES)
+def test_guard_gather(cuda, ov3d, N, F, bf16):
+    pts, depth, poses, feats, _ = _inputs(N, F)
+    i3, i2 = R.tables(pts, depth, poses, PAR)
+    f = F - 1
+    C = 17
+    rng = np.random.Generator(np.random.PCG64(N))
+    label = torch.from_numpy((rng.integers(-128, 128, (C, H * W)) / 16.0).astype(np.float32))
+    dt = torch.bfloat16 if bf16 else torch.float32
+    specs = {"label": In(label.to(dt)), "i3": In(torch.from_numpy(i3[f]), index=(0, 0)),
+             "i2": In(torch.from_numpy(i2[f]), index=(0, 1)), "out": Out((C, N), dt)}
+    out = guard.run_case(cuda, specs, lambda t: guard.call(
+        "ov3d_backproj_gather", t["label"], bf16, C, H * W, t["i3"], t["i2"], N, t["out"], like=t["label"]))
+    assert same(host(out["out"].float()), R.project(label.numpy().reshape(C, H, W), i3[f], i2[f], N))
+
+
+@pytest.mark.parametrize("rows", [0, 1], ids=["CN", "NC"])
+@pytest.mark.parametrize("bf16", [0, 1], ids=["f32", "bf16"])
+@pytest.mark.parametrize("N,F", GUARD_SHAPES)
+def test_guard_compose(cuda, ov3d, N, F, bf16, rows):
+    pts, depth, poses, feats, specs = _inputs(N, F)
+    C = 5
+    rng = np.random.Generator(np.random.PCG64(N + F))
+    feats = (rng.integers(-128, 128, (F, C, H, W)) / 16.0).astype(np.float32)
+    dt = torch.bfloat16 if bf16 else torch.float32
+    specs.update({"feat": In(torch.from_numpy(feats).to(dt)), "table": Out((F, R.ROW), torch.float32),
+                  "out": Out((N, C) if rows else (C, N), dt), "frame": Out((N,), torch.int32)})
+    out = guard.run_case(cuda, specs, lambda t: guard.call(
+        "ov3d_backproj_compose", t["pts"], N, t["depth"], t["poses"], F, t["params"], W, H, t["feat"],
+        bf16, C, rows, t["table"], t["out"], t["frame"], like=t["pts"]))
+    want, frame = R.compose(pts, depth, poses, feats, PAR)
+    assert same(host(out["out"].float()), np.ascontiguousarray(want.T) if rows else want)
+    assert same(host(out["frame"]), frame)
+
+
+@pytest.mark.parametrize("bad", [dict(N=0), dict(F=0), dict(W=0), dict(H=0), dict(W=65536, H=32768)])
+def test_guard_rejected_tables_write_nothing(cuda, ov3d, bad):
+    N, F = 65, 2
+    _, _, _, _, specs = _inputs(N, F)
+    a = dict(N=N, F=F, W=W, H=H)
+    a.update(bad)
+    specs.update({"table": Out((F, R.ROW), torch.float32), "counts": Out((F, 1), torch.int32),
+                  "i3": Out((F, N + 1), torch.int64), "i2": Out((F, N + 1), torch.int64)})
+    guard.run_case(cuda, specs, lambda t: guard.raw_call(
+        "ov3d_backproj_tables", t["pts"], a["N"], t["depth"], t["poses"], a["F"], t["params"], a["W"], a["H"],
+        t["table"], t["counts"], t["i3"], t["i2"], like=t["pts"]), expect_reject=True)
+
+
+@pytest.mark.parametrize("bad", [dict(N=0), dict(F=0), dict(C=0), dict(bf16=2), dict(rows=2), dict(H=0)])
+def test_guard_rejected_compose_and_gather_write_nothing(cuda, ov3d, bad):
+    N, F, C = 65, 2, 3
+    _, _, _, feats, specs = _inputs(N, F)
+    a = dict(N=N, F=F, C=C, bf16=0, rows=0, H=H)
+    a.update(bad)
+    specs.update({"feat": In(torch.from_numpy(feats)), "table": Out((F, R.ROW), torch.float32),
+                  "out": Out((C, N), torch.float32), "frame": Out((N,), torch.int32)})
+    guard.run_case(cuda, specs, lambda t: guard.raw_call(
+        "ov3d_backproj_compose", t["pts"], a["N"], t["depth"], t["poses"], a["F"], t["params"], W, a["H"],
+        t["feat"], a["bf16"], a["C"], a["rows"], t["table"], t["out"], t["frame"], like=t["pts"]), expect_reject=True)
+    if set(bad) & {"N", "C", "bf16", "H"}:
+        i = torch.zeros(N + 1, dtype=torch.int64)
+        gs = {"label": In(torch.from_numpy(feats[0])), "i3": In(i, index=(0, 0)), "i2": In(i, index=(0, 0)),
+              "out": Out((C, N), torch.float32)}
+        guard.run_case(cuda, gs, lambda t: guard.raw_call(
+            "ov3d_backproj_gather", t["label"], a["bf16"], a["C"], a["H"] * W, t["i3"], t["i2"], a["N"], t["out"],
+            like=t["label"]), expect_reject=True)
+
+
+# ---------------------------------------------------------------- into the training batch
+
+def test_composed_rows_are_the_batch_feature_2d(cuda, ov3d):
+    from ov3d_amd import projection, scannet
+    from ov3d_amd.dataset_config import ScannetDatasetConfig
+    g = gold("main")
+    N, C = len(g["points"]), 16
+    rng = np.random.Generator(np.random.PCG64(9))
+    feats = (rng.integers(-128, 128, (len(g["poses"]), C, H, W)) / 16.0).astype(np.float32)
+    rows, frame = projection.compose_features(g["points"], g["depth"], g["poses"], feats, rows=True)
+    rows_h = host(rows)
+    assert (host(frame) >= 0).sum() > 500
+    vert = np.concatenate([g["points"], np.full((N, 3), 128.0, np.float32)], 1)
+    ds = scannet.ScannetDetectionDataset(ScannetDatasetConfig(), split_set="val", num_points=512,
+                                         use_2d_feature=True, device=cuda, scans=[(vert, np.zeros((0, 7)))],
+                                         extras=[{"feature_2d": rows_h}])
+    batch = ds.get_batch([0], rng=np.random.RandomState(5))
+    choice = np.random.RandomState(5).choice(N, 512, replace=False)
+    assert same(host(batch["feature_2d"])[0], rows_h[choice])
+    assert host(batch["feature_2d"]).any()

@@ -13,6 +13,8 @@ Drop-in modules (reference module -> here):
   3DOVDet_tools scannet/lift_boxes.py     -> lift_boxes        (frustum lift, NMS, pool match on HIP)
   3DOVDet_tools scannet/evaluate_box.py,
     utils.evaluation.pr_helper.PRCalculator -> box_eval        (precision / recall of a split on HIP)
+  3DOVDet_tools scannet/assign_box_label_from_gt.py -> pool_label  (per-box label vote on HIP)
+  3DOVDet_tools scannet/assess_pseudo_label.py      -> label_assess (label confusion counts on HIP)
 The HIP kernels live in lib/libov3d_hip.so (C ABI: include/ov3d.h); there is
 no CPU fallback.
 """

@@ -125,6 +125,20 @@ def _read_backproj_header():
 BACKPROJ_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_backproj.h")
 _BACKPROJ_PROTOS = _read_backproj_header()
 BACKPROJ_EXPORTS = tuple(_BACKPROJ_PROTOS)
+
+
+def _read_poollabel_header():
+    """the pool labelling and label assessment entries (include/ov3d_poollabel.h,
+    csrc/poollabel.hip), read the same way"""
+    if not os.path.exists(POOLLABEL_HEADER_PATH):
+        raise NativeError(f"{POOLLABEL_HEADER_PATH} not found: the ctypes binding is derived from it")
+    with open(POOLLABEL_HEADER_PATH) as f:
+        return read_header(f.read())[1]
+
+
+POOLLABEL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_poollabel.h")
+_POOLLABEL_PROTOS = _read_poollabel_header()
+POOLLABEL_EXPORTS = tuple(_POOLLABEL_PROTOS)
 _STRUCTS = {}
 
 
@@ -145,7 +159,7 @@ def load():
                 "build it with `make -C open-vocabulary-3d-object-detection_amd/csrc`")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS, **_BOXEVAL_PROTOS,
-                                           **_BACKPROJ_PROTOS}.items():
+                                           **_BACKPROJ_PROTOS, **_POOLLABEL_PROTOS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -15,6 +15,7 @@ Drop-in modules (reference module -> here):
     utils.evaluation.pr_helper.PRCalculator -> box_eval        (precision / recall of a split on HIP)
   3DOVDet_tools scannet/assign_box_label_from_gt.py -> pool_label  (per-box label vote on HIP)
   3DOVDet_tools scannet/assess_pseudo_label.py      -> label_assess (label confusion counts on HIP)
+  datasets/scannet.py:272 (TODO: semantic labels)   -> open_vocab   (features x text arg max on MFMA)
 The HIP kernels live in lib/libov3d_hip.so (C ABI: include/ov3d.h); there is
 no CPU fallback.
 """

@@ -153,6 +153,19 @@ def _read_openvocab_header():
 OPENVOCAB_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_openvocab.h")
 _OPENVOCAB_PROTOS = _read_openvocab_header()
 OPENVOCAB_EXPORTS = tuple(_OPENVOCAB_PROTOS)
+
+
+def _read_liftview_header():
+    """the single-view lift entry (include/ov3d_liftview.h, csrc/liftview.hip), read the same way"""
+    if not os.path.exists(LIFTVIEW_HEADER_PATH):
+        raise NativeError(f"{LIFTVIEW_HEADER_PATH} not found: the ctypes binding is derived from it")
+    with open(LIFTVIEW_HEADER_PATH) as f:
+        return read_header(f.read())[1]
+
+
+LIFTVIEW_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_liftview.h")
+_LIFTVIEW_PROTOS = _read_liftview_header()
+LIFTVIEW_EXPORTS = tuple(_LIFTVIEW_PROTOS)
 _STRUCTS = {}
 
 
@@ -174,7 +187,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS, **_BOXEVAL_PROTOS,
                                            **_BACKPROJ_PROTOS, **_POOLLABEL_PROTOS,
-                                           **_OPENVOCAB_PROTOS}.items():
+                                           **_OPENVOCAB_PROTOS, **_LIFTVIEW_PROTOS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype

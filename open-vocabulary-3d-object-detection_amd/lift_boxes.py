@@ -17,6 +17,17 @@ synchronisation in between: the lift (``ov3d_lift_frustum`` over the vertices, o
 arithmetic (``ov3d_lift_nms``), the match against the proposal pool with the labelled pool rows
 (``ov3d_lift_match``), and the size NMS (``ov3d_lift_nms`` again).  One device-to-host copy.
 
+The scripts' ``VIEW='single'`` is ``lift_scannet_scan_single`` (``ScannetBoxLifter(view="single")``
+from files): no vertex cloud; a 2D box lifts every pixel of its frame whose class equals its
+label (the rectangle is not consulted, as in the reference) through depth, pose and alignment.
+Host: the halved copy of the intrinsic and numpy's inverse of it, the widened poses, the edge
+filter and the table of slots, one per distinct (frame, label) pair.  Device
+(csrc/liftview.hip behind include/ov3d_liftview.h): ``ov3d_liftview_frames``, one workgroup per
+slot and a second launch that gives every box its slot's bounds, then the same chain.  Depth is
+float32 metres or raw uint16 millimetres; per-frame labels may be a device int32 tensor (the
+first result of ``open_vocab.classify_frames``), which is read where it lies.  PIL decodes the
+PNGs of the file driver and is imported inside that call only.
+
 Number formats: 2D boxes keep the dtype they come in for the plane construction (as in the
 reference); the proposal pool and the alignment are taken as float64; float32 vertices are
 widened on the device.  Scores must be finite.  Ties between equal scores go to the higher row
@@ -35,6 +46,7 @@ from . import _native as nat
 NYU40IDS = np.array([3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39])
 SUNRGBD37IDS = (36, 4, 10, 29, 5, 12, 14, 8, 17, 35, 32, 18, 34, 6, 7, 25, 33)
 IGNORE_LABEL = -100
+PSEUDO_IGNORE_FROM = 18            # pseudo labels of this value and above are ignored
 DEPTH_MIN, DEPTH_MAX = 0.1, 10.0
 IMAGE_DIMS = (240, 320)            # the frames the 2D boxes live in; the intrinsic is 640 x 480
 MAX_PER_CLASS = 2048
@@ -216,6 +228,42 @@ def lift_image(depth, seg, lut, boxes, plabel, calib, rows, count=None):
     return count
 
 
+def lift_views(depth, seg, lut, ignore_from, kinv, pose, align, slot_frame, slot_label, box_slot, rows,
+               count=None):
+    """ov3d_liftview_frames: fills columns 0-5 of the device rows (M, ld) from the slot of every
+    box -> count (M) int32.  depth (F,H,W) float32 metres or uint16 raw millimetres; seg (F,H,W)
+    int32; lut (n) int32 or None; ignore_from: without a lut, seg >= ignore_from reads as -100
+    (None: off); kinv (3,3), pose (F,12) = R then t per frame, align (4,4), all float64."""
+    nat.check(depth, "depth", None, 3)
+    if depth.dtype not in (torch.float32, torch.uint16):
+        raise TypeError("depth: expected float32 or uint16")
+    F, H, W = depth.shape
+    _want(seg, "seg", torch.int32, (F, H, W))
+    _want(kinv, "kinv", torch.float64, (3, 3))
+    _want(pose, "pose", torch.float64, (F, 12))
+    _want(align, "align", torch.float64, (4, 4))
+    _want(slot_frame, "slot_frame", torch.int32, (None,))
+    S = slot_frame.shape[0]
+    _want(slot_label, "slot_label", torch.int32, (S,))
+    _want(box_slot, "box_slot", torch.int32, (None,))
+    M = box_slot.shape[0]
+    _want(rows, "rows", torch.float64, (M, None))
+    if lut is not None:
+        _want(lut, "lut", torch.int32, (None,))
+    if rows.shape[1] < 6 or min(F, H, W, S, M) < 1 or H * W >= 2 ** 31:
+        raise ValueError("rows: at least 6 columns; at least one pixel, slot and box; H * W < 2^31")
+    if count is None:
+        count = torch.empty(M, dtype=torch.int32, device=depth.device)
+    _want(count, "count", torch.int32, (M,))
+    slot_lohi = torch.empty(S, 6, dtype=torch.float64, device=depth.device)
+    slot_count = torch.empty(S, dtype=torch.int32, device=depth.device)
+    nat.call("ov3d_liftview_frames", depth, int(depth.dtype == torch.uint16), seg, lut,
+             0 if lut is None else lut.numel(), 2 ** 31 if ignore_from is None else int(ignore_from),
+             F, H, W, kinv, pose, align, slot_frame, slot_label, S, box_slot, M, slot_lohi, slot_count,
+             rows, rows.shape[1], count, like=depth)
+    return count
+
+
 def result_buffer(M, device):
     """one allocation for everything the host reads back: -> (packed uint8, out (M,10) f64,
     count (M) int32, rank2 (M) int32), the last three views of the first"""
@@ -309,6 +357,117 @@ def lift_scannet_scan(points, labels, axis_align_matrix, intrinsic, poses, boxes
     return final
 
 
+def nyu40_lut():
+    """nyu40 id -> class 0..17, -100 for every other id (ProjectionHelper.project_label)"""
+    lut = np.full(int(NYU40IDS.max()) + 1, IGNORE_LABEL, np.int32)
+    lut[NYU40IDS] = np.arange(len(NYU40IDS), dtype=np.int32)
+    return lut
+
+
+def single_host_plan(intrinsic, poses, boxes2d, image_dims=IMAGE_DIMS):
+    """Host side of the single-view mode -> dict(kinv (3,3) f64, pose (F,12) f64 = R then t per
+    frame, score_label (M,2), plabel (M) int32, slot_frame, slot_label (S) int32, box_slot (M)
+    int32).  The intrinsic is halved in a copy; its inverse is numpy's, of the float32 matrix,
+    widened.  The M boxes are those the edge filter leaves, frame by frame; a slot is a distinct
+    (frame, int label) pair, sorted by frame, then label."""
+    K = np.array(intrinsic, dtype=np.float32)
+    P = np.asarray(poses, dtype=np.float32)
+    if K.shape != (4, 4) or P.ndim != 3 or P.shape[1:] != (4, 4) or len(boxes2d) != P.shape[0]:
+        raise ValueError("intrinsic: expected (4,4); poses: (F,4,4), one per frame of boxes")
+    K[0] /= 2.0
+    K[1] /= 2.0
+    if not (np.isfinite(K).all() and np.isfinite(P).all()):
+        raise ValueError("intrinsic and poses must be finite (the device's min / max skip a NaN)")
+    kinv = np.linalg.inv(K[:3, :3]).astype(np.float64)
+    if not np.isfinite(kinv).all():
+        raise ValueError("intrinsic: its inverse is not finite")
+    P = P.astype(np.float64)
+    plan = dict(kinv=np.ascontiguousarray(kinv),
+                pose=np.ascontiguousarray(np.concatenate([P[:, :3, :3].reshape(-1, 9), P[:, :3, 3]], 1)))
+    frame, sl = [], []
+    for f, boxes in enumerate(boxes2d):
+        boxes = np.asarray(boxes)
+        _check_boxes(boxes)
+        boxes = edge_filter(boxes, image_dims)
+        frame.append(np.full(boxes.shape[0], f, np.int32))
+        sl.append(boxes[:, 4:6].astype(np.float64))
+    sl = np.concatenate(sl) if sl else np.zeros((0, 2))
+    frame = np.concatenate(frame) if frame else np.zeros(0, np.int32)
+    plabel = _box_labels(np.concatenate([np.zeros((len(sl), 4)), sl], 1))
+    _check_counts(plabel)
+    pairs, box_slot = np.unique(np.stack([frame, plabel], 1), axis=0, return_inverse=True)
+    return dict(plan, score_label=sl, plabel=plabel, slot_frame=np.ascontiguousarray(pairs[:, 0]),
+                slot_label=np.ascontiguousarray(pairs[:, 1]), box_slot=box_slot.reshape(-1).astype(np.int32))
+
+
+def _frames(x, name, dtypes):
+    """(F,H,W) frames: a device tensor as it is, anything else as one numpy array"""
+    if not isinstance(x, torch.Tensor):
+        x = np.asarray(x)
+    if x.ndim != 3 or (dtypes and x.dtype not in dtypes):
+        raise ValueError(f"{name}: expected (F,H,W)" + (f" of {' or '.join(map(str, dtypes))}" if dtypes else "")
+                         + f", got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def lift_scannet_scan_single(depths, labels, axis_align_matrix, intrinsic, poses, boxes2d, gss_pool,
+                             pseudo=True, nms=0.7, match=0.3, size_nms=0.0, device="cuda",
+                             return_lifted=False):
+    """One ScanNet scan in the reference's ``VIEW='single'`` mode -> what lift_scannet_scan
+    returns.  Every 2D box lifts all pixels of its frame whose class equals its label (the
+    rectangle is not consulted, as in the reference) through depth, pose and alignment.
+
+    depths (F,H,W): float32 metres or uint16 raw millimetres (read as raw / 1000 in float32),
+    numpy or a device tensor.  labels (F,H,W): numpy of any number type, or a device int32
+    tensor such as the first result of open_vocab.classify_frames, which is used where it is.
+    pseudo=True: class indices, values >= 18 ignored (negatives stay); pseudo=False: nyu40 ids,
+    mapped to 0..17 on the device, every other id ignored.  The edge filter uses the frames' own
+    (H, W).  Poses, intrinsic, alignment and host depths must be finite (ValueError); for a
+    device float depth tensor that is the caller's precondition."""
+    pool = _pool(gss_pool)
+    A = np.ascontiguousarray(np.asarray(axis_align_matrix, dtype=np.float64))
+    if A.shape != (4, 4) or not np.isfinite(A).all():
+        raise ValueError("axis_align_matrix: expected a finite (4,4)")
+    depths = _frames(depths, "depths", (torch.float32, torch.uint16) if isinstance(depths, torch.Tensor)
+                     else (np.dtype(np.float32), np.dtype(np.uint16)))
+    labels = _frames(labels, "labels", (torch.int32,) if isinstance(labels, torch.Tensor) else ())
+    if tuple(depths.shape) != tuple(labels.shape) or depths.shape[0] != len(boxes2d):
+        raise ValueError(f"depths {tuple(depths.shape)} and labels {tuple(labels.shape)}: expected the "
+                         f"same (F,H,W) with one frame per list of boxes ({len(boxes2d)})")
+    host_d, host_l = not isinstance(depths, torch.Tensor), not isinstance(labels, torch.Tensor)
+    if host_d and depths.dtype.kind == "f" and not np.isfinite(depths).all():
+        raise ValueError("depths must be finite (the device's min / max skip a NaN)")
+    plan = single_host_plan(intrinsic, poses, boxes2d, tuple(depths.shape[1:]))
+    M = plan["box_slot"].shape[0]
+    if M == 0 or depths.shape[1] * depths.shape[2] == 0:
+        empty = np.zeros((0, 7))
+        return (empty, np.zeros((0, 8))) if return_lifted else empty
+    dev = labels.device if not host_l else depths.device if not host_d else torch.device(device)
+    slot_frame, pose = plan["slot_frame"], plan["pose"]
+    if host_d and host_l:                                  # upload the frames that hold a slot only
+        used, slot_frame = np.unique(slot_frame, return_inverse=True)
+        depths, labels, pose = depths[used], labels[used], pose[used]
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    if host_d:
+        depths = up(depths)
+    if host_l:
+        labels = up(_int_labels(labels, _NEVER_POINT))
+    rows_h = np.zeros((M, 8))
+    rows_h[:, 6:] = plan["score_label"]
+    rows = up(rows_h)
+    packed, out, count, rank2 = result_buffer(M, dev)
+    lift_views(depths.contiguous(), labels.contiguous(), None if pseudo else up(nyu40_lut()),
+               PSEUDO_IGNORE_FROM if pseudo else None, up(plan["kinv"]), up(pose), up(A),
+               up(slot_frame.reshape(-1).astype(np.int32)), up(plan["slot_label"]), up(plan["box_slot"]),
+               rows, count)
+    chain_tail(rows, count, up(pool), out, rank2, nms, match, size_nms)
+    final = _finish(packed, M, 7)
+    if return_lifted:
+        r, c = rows.cpu().numpy(), count.cpu().numpy()
+        return final, r[c > 0]
+    return final
+
+
 def lift_sunrgbd_scan(depth, seg, Rtilt, K, boxes2d, gss_pool, nms=0.7, match=0.3, size_nms=0.0,
                       device="cuda", return_lifted=False):
     """One SUN RGB-D image -> the array the reference saves ((0,8) when nothing was lifted).
@@ -384,17 +543,60 @@ class ScannetBoxLifter:
                                         this listing, sorted as the reference sorts its frames
     gss_dir/<scan>_prop.npy         (P,7) proposals
     scans_dir/<scan>/<scan>.txt     the axisAlignment line
+
+    view="single" (the reference's ``VIEW='single'``; lift_scannet_scan_single) reads instead
+    of the vertex file, and decodes PNGs with PIL, imported only then:
+    label_dir/<scan>.npy            the per-frame class maps open_vocab.save_frame_labels writes:
+                                    a pickled dict {int(frame id): (H,W) map}, because that is the
+                                    file the reference's single-view branch loads (allow_pickle
+                                    on: open files you trust only); used with pseudo=True
+    frames_dir/<scan>/depth/<id>.png         16-bit depth in millimetres
+    frames_dir/<scan>/label-mapped/<id>.png  nyu40 ids, read in place of the dict file with
+                                             pseudo=False (the reference's PSEUDO_FLAG = False)
     """
 
     def __init__(self, label_dir, frames_dir, boxes2d_dir, gss_dir, scans_dir, out_dir, nms=0.7,
-                 match=0.3, size_nms=0.0, device="cuda"):
+                 match=0.3, size_nms=0.0, device="cuda", view="multi", pseudo=True):
+        if view not in ("multi", "single"):
+            raise ValueError(f"view: 'multi' or 'single', got {view!r}")
         self.label_dir, self.frames_dir, self.boxes2d_dir = label_dir, frames_dir, boxes2d_dir
         self.gss_dir, self.scans_dir, self.out_dir = gss_dir, scans_dir, out_dir
         self.nms, self.match, self.size_nms, self.device = nms, match, size_nms, device
+        self.view, self.pseudo = view, pseudo
+
+    def _lift_one_single(self, scan, frames, box_dir):
+        from PIL import Image
+
+        def png(kind, f):
+            with Image.open(os.path.join(self.frames_dir, scan, kind, f + ".png")) as im:
+                return np.array(im)
+        depths = np.stack([png("depth", f) for f in frames])
+        if depths.dtype != np.uint16:
+            if depths.dtype.kind not in "iu" or depths.min() < 0 or depths.max() >= 2 ** 16:
+                raise ValueError(f"{scan}: depth PNGs are not 16-bit")
+            depths = depths.astype(np.uint16)
+        if self.pseudo:
+            from . import open_vocab
+            labels = open_vocab.load_frame_labels(os.path.join(self.label_dir, scan + ".npy"), frames)
+        else:
+            labels = np.stack([png("label-mapped", f) for f in frames])
+        frame_dir = os.path.join(self.frames_dir, scan)
+        return lift_scannet_scan_single(
+            depths, labels, read_alignment(os.path.join(self.scans_dir, scan, scan + ".txt")),
+            read_pose(os.path.join(frame_dir, "intrinsic_depth.txt")),
+            [read_pose(os.path.join(frame_dir, "pose", f + ".txt")) for f in frames],
+            [np.load(os.path.join(box_dir, f + ".npy"), allow_pickle=False) for f in frames],
+            np.load(os.path.join(self.gss_dir, scan + "_prop.npy"), allow_pickle=False),
+            self.pseudo, self.nms, self.match, self.size_nms, self.device)
 
     def lift_one(self, scan):
         box_dir = os.path.join(self.boxes2d_dir, scan, "color")
         frames = [n.split(".")[0] for n in sorted(os.listdir(box_dir))]
+        if self.view == "single":
+            out = self._lift_one_single(scan, frames, box_dir)
+            os.makedirs(self.out_dir, exist_ok=True)
+            np.save(os.path.join(self.out_dir, scan + "_bbox.npy"), out)
+            return out.shape[0]
         sem = np.load(os.path.join(self.label_dir, scan + ".npy"), allow_pickle=False)
         frame_dir = os.path.join(self.frames_dir, scan)
         out = lift_scannet_scan(

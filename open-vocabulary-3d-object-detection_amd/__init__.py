@@ -16,6 +16,9 @@ Drop-in modules (reference module -> here):
   3DOVDet_tools scannet/assign_box_label_from_gt.py -> pool_label  (per-box label vote on HIP)
   3DOVDet_tools scannet/assess_pseudo_label.py      -> label_assess (label confusion counts on HIP)
   datasets/scannet.py:272 (TODO: semantic labels)   -> open_vocab   (features x text arg max on MFMA)
+  (none: compute_objectness_and_cls_prob asserts the
+    training class count)                           -> detect       (queries x any vocabulary -> detections:
+                                                                     streamed softmax and top-k on MFMA)
 The HIP kernels live in lib/libov3d_hip.so (C ABI: include/ov3d.h); there is
 no CPU fallback.
 """

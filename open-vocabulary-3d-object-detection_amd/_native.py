@@ -166,6 +166,19 @@ def _read_liftview_header():
 LIFTVIEW_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_liftview.h")
 _LIFTVIEW_PROTOS = _read_liftview_header()
 LIFTVIEW_EXPORTS = tuple(_LIFTVIEW_PROTOS)
+
+
+def _read_detect_header():
+    """the vocabulary scoring entry (include/ov3d_detect.h, csrc/vocabscore.hip), read the same way"""
+    if not os.path.exists(DETECT_HEADER_PATH):
+        raise NativeError(f"{DETECT_HEADER_PATH} not found: the ctypes binding is derived from it")
+    with open(DETECT_HEADER_PATH) as f:
+        return read_header(f.read())[1]
+
+
+DETECT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_detect.h")
+_DETECT_PROTOS = _read_detect_header()
+DETECT_EXPORTS = tuple(_DETECT_PROTOS)
 _STRUCTS = {}
 
 
@@ -187,7 +200,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS, **_BOXEVAL_PROTOS,
                                            **_BACKPROJ_PROTOS, **_POOLLABEL_PROTOS,
-                                           **_OPENVOCAB_PROTOS, **_LIFTVIEW_PROTOS}.items():
+                                           **_OPENVOCAB_PROTOS, **_LIFTVIEW_PROTOS,
+                                           **_DETECT_PROTOS}.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype

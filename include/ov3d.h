@@ -1175,10 +1175,9 @@ int ov3d_stamps_count(void);
 int ov3d_stamps_get(int i, int* kind, long long* word_off, long long* waves, long long* work);
 long long ov3d_wall_clock_khz(void);
 
-/* The pseudo-box lifting entries of the same library (csrc/lift.hip: ov3d_lift_frustum,
- * ov3d_lift_image, ov3d_lift_nms, ov3d_lift_match) are declared in include/ov3d_lift.h, the
- * box evaluation entries (csrc/boxeval.hip: ov3d_boxeval_match, ov3d_boxeval_tally) in
- * include/ov3d_boxeval.h. */
+/* The offline label and pseudo-box entries of the same library are declared by feature in the
+ * include/ov3d_*.h beside this file.  ov3d_amd._native reads every one of them with one reader;
+ * a function or struct name is declared in one header only. */
 
 #ifdef __cplusplus
 }

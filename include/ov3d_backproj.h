@@ -2,10 +2,8 @@
  *
  * Frame features -> per-vertex features (utils/projection.py ProjectionHelper.compute_projection
  * and .project, utils/image_util.py image_processor.compute_projection).  ov3d_amd.projection
- * drives these entries; ov3d_amd._native derives their ctypes signatures from this file with the
- * reader it uses for include/ov3d.h.  The prototypes live in a header of their own because the
- * closed set of tests/guard_cases.py is keyed on include/ov3d.h; their guard-band cases are in
- * tests/test_backproj_gpu.py.
+ * drives these entries; ov3d_amd._native derives their ctypes signatures from this file, as
+ * from every include/ov3d*.h; their guard-band cases are in tests/test_backproj_gpu.py.
  *
  * All arithmetic is float32 without contraction (the world-to-camera inverse alone is formed in
  * float64 and rounded), every sum in the order written here; tests/backproj_ref.py restates it

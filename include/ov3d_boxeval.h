@@ -4,9 +4,8 @@
  * at up to OV3D_BOXEVAL_MAX_T IoU thresholds at once (3DOVDet_tools/scannet/evaluate_box.py with
  * utils/evaluation/pr_helper.py PRCalculator, eval_det.py eval_det_cls and get_iou, and
  * evaluation/box_util.py calc_iou).  ov3d_amd.box_eval drives these entries; ov3d_amd._native
- * derives their ctypes signatures from this file with the reader it uses for include/ov3d.h.
- * The prototypes live in a header of their own because the closed set of tests/guard_cases.py
- * is keyed on include/ov3d.h; their guard-band cases are in tests/test_box_eval_gpu.py.
+ * derives their ctypes signatures from this file, as from every include/ov3d*.h; their
+ * guard-band cases are in tests/test_box_eval_gpu.py.
  *
  * All arithmetic is float64 without contraction, in the reference's order.  Every entry
  * validates its arguments and returns OV3D_EINVAL before any launch; stream is the HIP stream

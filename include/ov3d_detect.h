@@ -5,9 +5,7 @@
  * model's visual_embeds to detections under any list of names.  The reference has no such
  * code (its compute_objectness_and_cls_prob asserts the training class count).
  * ov3d_amd.detect drives the entry; ov3d_amd._native derives its ctypes signature from this
- * file with the reader it uses for include/ov3d.h.  The prototype lives in a header of its own
- * because the closed set of tests/guard_cases.py is keyed on include/ov3d.h; its guard-band
- * cases are in tests/test_detect_gpu.py.
+ * file, as from every include/ov3d*.h; its guard-band cases are in tests/test_detect_gpu.py.
  *
  * The entry validates its arguments and returns OV3D_EINVAL before any launch; stream is the
  * HIP stream (NULL: the default stream).  One launch, nothing synchronises, no atomics; legal

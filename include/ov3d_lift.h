@@ -3,10 +3,8 @@
  * Stage 3 of the open-vocabulary pipeline: 2D detections + per-point (ScanNet) or per-pixel
  * (SUN RGB-D) labels -> 3D pseudo boxes (3DOVDet_tools/{scannet,sunrgbd}/lift_boxes.py with
  * utils/projection.py and utils/box_3d_utils.py).  ov3d_amd.lift_boxes drives these entries;
- * ov3d_amd._native derives their ctypes signatures from this file with the reader it uses for
- * include/ov3d.h.  The prototypes live in a header of their own because the closed set of
- * tests/guard_cases.py is keyed on include/ov3d.h; their guard-band cases are in
- * tests/test_lift_gpu.py.
+ * ov3d_amd._native derives their ctypes signatures from this file, as from every
+ * include/ov3d*.h; their guard-band cases are in tests/test_lift_gpu.py.
  *
  * All arithmetic is float64 without contraction, in the reference's order wherever an order is
  * specified there.  Every entry validates its arguments and returns OV3D_EINVAL before any

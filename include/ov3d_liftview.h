@@ -5,10 +5,8 @@
  * depth map, the camera pose and the alignment matrix.  The lifted box depends on (frame, label)
  * only, so the host deduplicates the 2D boxes into slots, one per distinct pair; the cost
  * follows the slots, not the boxes.  ov3d_amd.lift_boxes drives the entry; ov3d_amd._native
- * derives its ctypes signature from this file with the reader it uses for include/ov3d.h.  The
- * prototype lives in a header of its own: the set of include/ov3d_lift.h is pinned by its tests
- * and the closed set of tests/guard_cases.py is keyed on include/ov3d.h; the guard-band cases
- * are in tests/test_lift_single_gpu.py.
+ * derives its ctypes signature from this file, as from every include/ov3d*.h; the guard-band
+ * cases are in tests/test_lift_single_gpu.py.
  *
  * All arithmetic is float64 without contraction in the order stated below.  The entry validates
  * its arguments and returns OV3D_EINVAL before any launch; stream is the HIP stream (NULL: the

@@ -5,9 +5,8 @@
  * the step the reference leaves open (datasets/scannet.py:272, "TODO: acquire semantic labels
  * using LSeg / OpenSeg + projection") and whose results its tools read from disk.
  * ov3d_amd.open_vocab drives the entry; ov3d_amd._native derives its ctypes signature from this
- * file with the reader it uses for include/ov3d.h.  The prototype lives in a header of its own
- * because the closed set of tests/guard_cases.py is keyed on include/ov3d.h; its guard-band
- * cases are in tests/test_open_vocab_gpu.py.
+ * file, as from every include/ov3d*.h; its guard-band cases are in
+ * tests/test_open_vocab_gpu.py.
  *
  * The entry validates its arguments and returns OV3D_EINVAL before any launch; stream is the
  * HIP stream (NULL: the default stream).  One launch, nothing synchronises, no atomics; legal

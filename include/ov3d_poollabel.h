@@ -6,9 +6,8 @@
  * counts the agreement of per-pixel pseudo labels with ground-truth frames
  * (3DOVDet_tools/scannet/assess_pseudo_label.py, match).  ov3d_amd.pool_label and
  * ov3d_amd.label_assess drive them; ov3d_amd._native derives their ctypes signatures from this
- * file with the reader it uses for include/ov3d.h.  The prototypes live in a header of their own
- * because the closed set of tests/guard_cases.py is keyed on include/ov3d.h; their guard-band
- * cases are in tests/test_pool_label_gpu.py.
+ * file, as from every include/ov3d*.h; their guard-band cases are in
+ * tests/test_pool_label_gpu.py.
  *
  * Both are integer decisions: no floating-point arithmetic happens on the device, only the
  * exact widening of a float32 vertex to double and compares.  Every entry validates its

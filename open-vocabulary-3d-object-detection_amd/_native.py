@@ -1,4 +1,5 @@
-"""ctypes binding of ``lib/libov3d_hip.so`` (the C ABI declared in include/ov3d.h).
+"""ctypes binding of ``lib/libov3d_hip.so`` (the C ABI declared in include/ov3d.h and the
+include/ov3d_*.h beside it).
 
 This is the only door from Python to the hot-path kernels.  There is no CPU
 fallback: if the library is missing, or a tensor is not on a ROCm device, the
@@ -7,6 +8,7 @@ HIP stream on the tensor's device, so every op is stream-ordered with the
 surrounding torch work and capturable into a hipGraph.
 """
 import ctypes
+import glob
 import os
 import re
 
@@ -26,7 +28,7 @@ class NativeError(RuntimeError):
     pass
 
 
-# The closed set of C types include/ov3d.h uses.  Any pointer is a c_void_p, so that
+# The closed set of C types the headers use.  Any pointer is a c_void_p, so that
 # data_ptr() ints, None and byref() all pass.
 _SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float,
             "double": ctypes.c_double}
@@ -77,113 +79,35 @@ def read_header(text):
     return structs, protos
 
 
-def _read_own_header():
-    if not os.path.exists(HEADER_PATH):
-        raise NativeError(f"{HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(HEADER_PATH) as f:
-        return read_header(f.read())
+def read_headers(paths):
+    """header files -> ({struct: fields}, {function: prototype}, {file name: its functions}); a
+    missing file, or a function or struct name declared in two of them, raises NativeError"""
+    structs, protos, exports, owner = {}, {}, {}, {}
+    for path in paths:
+        if not os.path.exists(path):
+            raise NativeError(f"{path} not found: the ctypes binding is derived from it")
+        with open(path) as f:
+            s, p = read_header(f.read())
+        for name in (*s, *p):
+            if name in owner:
+                raise NativeError(f"`{name}` is declared in both {owner[name]} and {path}")
+            owner[name] = path
+        structs.update(s)
+        protos.update(p)
+        exports[os.path.basename(path)] = tuple(p)
+    return structs, protos, exports
 
 
-_STRUCT_FIELDS, _PROTOS = _read_own_header()
+# One reader for every header: include/ov3d.h, then each feature's include/ov3d_*.h as the
+# directory lists them, so a header added later is bound without a change here.
+HEADER_PATHS = (HEADER_PATH, *sorted(glob.glob(os.path.join(os.path.dirname(HEADER_PATH), "ov3d_*.h"))))
+_STRUCT_FIELDS, _PROTOS, HEADER_EXPORTS = read_headers(HEADER_PATHS)
 EXPORTS = tuple(_PROTOS)
-
-
-def _read_lift_header():
-    """the lifting entries (include/ov3d_lift.h, csrc/lift.hip), read the same way"""
-    if not os.path.exists(LIFT_HEADER_PATH):
-        raise NativeError(f"{LIFT_HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(LIFT_HEADER_PATH) as f:
-        return read_header(f.read())[1]
-
-
-LIFT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_lift.h")
-_LIFT_PROTOS = _read_lift_header()
-LIFT_EXPORTS = tuple(_LIFT_PROTOS)
-
-
-def _read_boxeval_header():
-    """the box evaluation entries (include/ov3d_boxeval.h, csrc/boxeval.hip), read the same way"""
-    if not os.path.exists(BOXEVAL_HEADER_PATH):
-        raise NativeError(f"{BOXEVAL_HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(BOXEVAL_HEADER_PATH) as f:
-        return read_header(f.read())[1]
-
-
-BOXEVAL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_boxeval.h")
-_BOXEVAL_PROTOS = _read_boxeval_header()
-BOXEVAL_EXPORTS = tuple(_BOXEVAL_PROTOS)
-
-
-def _read_backproj_header():
-    """the back-projection entries (include/ov3d_backproj.h, csrc/backproj.hip), read the same way"""
-    if not os.path.exists(BACKPROJ_HEADER_PATH):
-        raise NativeError(f"{BACKPROJ_HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(BACKPROJ_HEADER_PATH) as f:
-        return read_header(f.read())[1]
-
-
-BACKPROJ_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_backproj.h")
-_BACKPROJ_PROTOS = _read_backproj_header()
-BACKPROJ_EXPORTS = tuple(_BACKPROJ_PROTOS)
-
-
-def _read_poollabel_header():
-    """the pool labelling and label assessment entries (include/ov3d_poollabel.h,
-    csrc/poollabel.hip), read the same way"""
-    if not os.path.exists(POOLLABEL_HEADER_PATH):
-        raise NativeError(f"{POOLLABEL_HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(POOLLABEL_HEADER_PATH) as f:
-        return read_header(f.read())[1]
-
-
-POOLLABEL_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_poollabel.h")
-_POOLLABEL_PROTOS = _read_poollabel_header()
-POOLLABEL_EXPORTS = tuple(_POOLLABEL_PROTOS)
-
-
-def _read_openvocab_header():
-    """the open-vocabulary classification entry (include/ov3d_openvocab.h, csrc/openvocab.hip),
-    read the same way"""
-    if not os.path.exists(OPENVOCAB_HEADER_PATH):
-        raise NativeError(f"{OPENVOCAB_HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(OPENVOCAB_HEADER_PATH) as f:
-        return read_header(f.read())[1]
-
-
-OPENVOCAB_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_openvocab.h")
-_OPENVOCAB_PROTOS = _read_openvocab_header()
-OPENVOCAB_EXPORTS = tuple(_OPENVOCAB_PROTOS)
-
-
-def _read_liftview_header():
-    """the single-view lift entry (include/ov3d_liftview.h, csrc/liftview.hip), read the same way"""
-    if not os.path.exists(LIFTVIEW_HEADER_PATH):
-        raise NativeError(f"{LIFTVIEW_HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(LIFTVIEW_HEADER_PATH) as f:
-        return read_header(f.read())[1]
-
-
-LIFTVIEW_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_liftview.h")
-_LIFTVIEW_PROTOS = _read_liftview_header()
-LIFTVIEW_EXPORTS = tuple(_LIFTVIEW_PROTOS)
-
-
-def _read_detect_header():
-    """the vocabulary scoring entry (include/ov3d_detect.h, csrc/vocabscore.hip), read the same way"""
-    if not os.path.exists(DETECT_HEADER_PATH):
-        raise NativeError(f"{DETECT_HEADER_PATH} not found: the ctypes binding is derived from it")
-    with open(DETECT_HEADER_PATH) as f:
-        return read_header(f.read())[1]
-
-
-DETECT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "ov3d_detect.h")
-_DETECT_PROTOS = _read_detect_header()
-DETECT_EXPORTS = tuple(_DETECT_PROTOS)
 _STRUCTS = {}
 
 
 def struct(name):
-    """the ctypes.Structure of a struct of include/ov3d.h (fields in the header's order)"""
+    """the ctypes.Structure of a struct of the headers (fields in its header's order)"""
     if name not in _STRUCTS:
         _STRUCTS[name] = type(name, (ctypes.Structure,), {"_fields_": _STRUCT_FIELDS[name]})
     return _STRUCTS[name]
@@ -198,10 +122,7 @@ def load():
                 f"{LIB_PATH} not found: the HIP extension is required (no CPU fallback); "
                 "build it with `make -C open-vocabulary-3d-object-detection_amd/csrc`")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**_PROTOS, **_LIFT_PROTOS, **_BOXEVAL_PROTOS,
-                                           **_BACKPROJ_PROTOS, **_POOLLABEL_PROTOS,
-                                           **_OPENVOCAB_PROTOS, **_LIFTVIEW_PROTOS,
-                                           **_DETECT_PROTOS}.items():
+        for name, (restype, argtypes) in _PROTOS.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -21,6 +21,7 @@
 #include <float.h>
 #include <limits.h>
 
+#include "boxreduce.h"
 #include "common.h"
 #include "../../include/ov3d_lift.h"
 
@@ -29,6 +30,7 @@ namespace {
 constexpr int kLiftThreads = 256;
 constexpr int kNmsThreads = 1024;
 constexpr int kWaves = kLiftThreads / 64;
+static_assert(kLiftThreads == kBoxThreads, "box_reduce_store reduces a workgroup of kBoxThreads");
 
 __device__ __forceinline__ double map_row(const double* m, double x, double y, double z) {
     return ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
@@ -53,52 +55,13 @@ lift_prep_kernel(const T* __restrict__ pts, int N, const double* __restrict__ al
     w[5] = map_row(align + 8, ox, oy, oz);
 }
 
-// Workgroup reduction of a running box (lo, hi, n) and the write of one (6) row + count.
-// red: 7 * kWaves doubles of LDS (224 B).
-__device__ __forceinline__ void box_reduce_store(double lo[3], double hi[3], int n, double* red,
-                                                 double* lohi_row, int32_t* count) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fmin(lo[a], __shfl_xor(lo[a], off, 64));
-            hi[a] = fmax(hi[a], __shfl_xor(hi[a], off, 64));
-        }
-        n += __shfl_xor(n, off, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            red[wave * 7 + a] = lo[a];
-            red[wave * 7 + 3 + a] = hi[a];
-        }
-        red[wave * 7 + 6] = (double)n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-        for (int w = 0; w < kWaves; ++w) total += (int)red[w * 7 + 6];
-        for (int a = 0; a < 3; ++a) {
-            double l = red[a], h = red[3 + a];
-            for (int w = 1; w < kWaves; ++w) {
-                l = fmin(l, red[w * 7 + a]);
-                h = fmax(h, red[w * 7 + 3 + a]);
-            }
-            lohi_row[a] = total ? l : 0.0;
-            lohi_row[3 + a] = total ? h : 0.0;
-        }
-        *count = total;
-    }
-}
-
 // one workgroup per frustum over all points; only points of the frustum's label are tested
 __global__ void __launch_bounds__(kLiftThreads)
 lift_frustum_kernel(const double* __restrict__ ws, const int32_t* __restrict__ labels, int N,
                     const double* __restrict__ planes, const int32_t* __restrict__ plabel,
                     double* __restrict__ lohi, int ld, int32_t* __restrict__ count) {
     __shared__ double pl[24];
-    __shared__ double red[7 * kWaves];
+    __shared__ double red[7 * kBoxWaves];
     const int m = blockIdx.x;
     if (threadIdx.x < 24) pl[threadIdx.x] = planes[(long long)m * 24 + threadIdx.x];
     __syncthreads();
@@ -138,7 +101,7 @@ lift_image_kernel(const D* __restrict__ depth, const int32_t* __restrict__ seg,
                   const double* __restrict__ boxes, const int32_t* __restrict__ plabel,
                   const double* __restrict__ calib, double* __restrict__ lohi, int ld,
                   int32_t* __restrict__ count) {
-    __shared__ double red[7 * kWaves];
+    __shared__ double red[7 * kBoxWaves];
     const int b = blockIdx.x;
     const double x = boxes[6ll * b], y = boxes[6ll * b + 1];
     const double xw = x + boxes[6ll * b + 2], yh = y + boxes[6ll * b + 3];

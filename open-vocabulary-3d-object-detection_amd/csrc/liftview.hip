@@ -5,17 +5,18 @@
 // a second launch copies every box's slot into its row.  Everything is float64; the file is
 // built with -ffp-contract=off (Makefile), so a * b + c is two roundings as in numpy.  Min, max
 // and integer counts are order-independent, so the result is deterministic whatever the
-// reduction shape.  The reduction restates box_reduce_store of lift.hip, which stays as it is.
+// reduction shape.
 #include <float.h>
 #include <limits.h>
 
+#include "boxreduce.h"
 #include "common.h"
 #include "../../include/ov3d_liftview.h"
 
 namespace {
 
 constexpr int kViewThreads = 256;
-constexpr int kViewWaves = kViewThreads / 64;
+static_assert(kViewThreads == kBoxThreads, "box_reduce_store reduces a workgroup of kBoxThreads");
 constexpr int kViewUnroll = 4;          // label loads in flight per thread
 
 __device__ __forceinline__ float depth_metres(const float* d, long long at) { return d[at]; }
@@ -25,7 +26,7 @@ __device__ __forceinline__ float depth_metres(const uint16_t* d, long long at) {
 }
 
 // One workgroup per slot streams the slot's label map; depth is read and a point computed for
-// matching pixels only.  LDS: 7 * kViewWaves doubles (224 B).
+// matching pixels only.  LDS: 7 * kBoxWaves doubles (224 B).
 template <typename D>
 __global__ void __launch_bounds__(kViewThreads)
 liftview_slot_kernel(const D* __restrict__ depth, const int32_t* __restrict__ seg,
@@ -35,7 +36,7 @@ liftview_slot_kernel(const D* __restrict__ depth, const int32_t* __restrict__ se
                      const int32_t* __restrict__ slot_frame,
                      const int32_t* __restrict__ slot_label, double* __restrict__ slot_lohi,
                      int32_t* __restrict__ slot_count) {
-    __shared__ double red[7 * kViewWaves];
+    __shared__ double red[7 * kBoxWaves];
     const int s = blockIdx.x;
     const int f = slot_frame[s], lab = slot_label[s];
     const int npix = (f >= 0 && f < F) ? HW : 0;      // uniform: a foreign frame holds no pixel
@@ -78,39 +79,7 @@ liftview_slot_kernel(const D* __restrict__ depth, const int32_t* __restrict__ se
             ++n;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fmin(lo[a], __shfl_xor(lo[a], off, 64));
-            hi[a] = fmax(hi[a], __shfl_xor(hi[a], off, 64));
-        }
-        n += __shfl_xor(n, off, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            red[wave * 7 + a] = lo[a];
-            red[wave * 7 + 3 + a] = hi[a];
-        }
-        red[wave * 7 + 6] = (double)n;                 // at most H * W < 2^31: exact
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-        for (int w = 0; w < kViewWaves; ++w) total += (int)red[w * 7 + 6];
-        for (int a = 0; a < 3; ++a) {
-            double l = red[a], h = red[3 + a];
-            for (int w = 1; w < kViewWaves; ++w) {
-                l = fmin(l, red[w * 7 + a]);
-                h = fmax(h, red[w * 7 + 3 + a]);
-            }
-            slot_lohi[6ll * s + a] = total ? l : 0.0;
-            slot_lohi[6ll * s + 3 + a] = total ? h : 0.0;
-        }
-        slot_count[s] = total;
-    }
+    box_reduce_store(lo, hi, n, red, slot_lohi + 6ll * s, slot_count + s);   // n <= H * W < 2^31
 }
 
 // every 2D box takes the result of its slot: columns 0-5 of its row, and its count

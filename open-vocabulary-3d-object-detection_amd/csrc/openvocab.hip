@@ -7,37 +7,20 @@
 // a wave per channel, 64 consecutive pixels), then every wave runs the MFMAs of its 16 rows
 // against every tile of 16 text rows.  The text is the A operand and the features the B
 // operand, so a lane's accumulators hold 4 text rows of ONE feature row: the arg max is a scan
-// of the lane's registers and two xor steps over the four lanes that share the row.
-//
-// LDS rows are 136 bytes apart (128 + 8): fragments are read 8 bytes at a time.
+// of the lane's registers and two xor steps over the four lanes that share the row.  The
+// LDS row pitch, the chunk and the fragment read are textdot.h's, shared with vocabscore.hip.
 #include <limits.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include "textdot.h"
 #include "../../include/ov3d_openvocab.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int kRows = OV3D_OPENVOCAB_ROWS;
 constexpr int kThreads = 256;
-constexpr int kChunk = 128;      // bytes of a row per K-chunk
-constexpr int kStride = 136;     // LDS row pitch in bytes
-
-struct alignas(8) Frag {         // 16 bytes of an LDS row, 8-byte aligned
-    uint2 lo, hi;
-};
-
-__device__ __forceinline__ Frag lds_frag(const unsigned char* p) {
-    Frag f;
-    f.lo = *reinterpret_cast<const uint2*>(p);
-    f.hi = *reinterpret_cast<const uint2*>(p + 8);
-    return f;
-}
 
 // rows layout (features and text): `rows` LDS rows from src rows row0 .., the first `valid` of
 // them exist; channels k0 .. k0 + KC - 1, those >= C zero

@@ -1,9 +1,7 @@
 // Vocabulary scoring (include/ov3d_detect.h): R query embeddings against the (T, C) text
 // embeddings -> objectness, log-sum-exp and the K most probable classes, one launch.
 //
-// The dot products are those of openvocab.hip: 16 feature rows per MFMA, the channels in chunks
-// of 128 bytes of a row staged in LDS (136-byte pitch, fragments read 8 bytes at a time), the
-// text the A operand and the features the B operand, so a lane's accumulators hold 4 text rows
+// The dot products are those of openvocab.hip (textdot.h): a lane's accumulators hold 4 text rows
 // per 16-row text block of ONE feature row.  The vocabulary goes by in tiles of 256 text rows
 // (16 blocks).  After a tile's channels the lanes of a row agree on the new maximum, every lane
 // rescales its own partial sums and adds its own terms, and offers its scores to its own sorted
@@ -24,33 +22,16 @@
 #include <limits.h>
 #include <math.h>
 
-#include <type_traits>
-
 #include "common.h"
+#include "textdot.h"
 #include "../../include/ov3d_detect.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int kChunk = 128;      // bytes of a row per K-chunk
-constexpr int kStride = 136;     // LDS row pitch in bytes
 constexpr int kTT = OV3D_DETECT_TILE_T / 16;
 constexpr int kOne = 0, kRows = 1, kSplit = 2;
 constexpr int kSplitMaxK = 8;    // K above it: kOne (the lists of 256 threads would not fit 64 KB)
 constexpr int kExchange = 4 * 64 * 4;   // bytes: tile maxima, sums, background terms, flags of 4 waves x 16 rows
-
-struct alignas(8) Frag {         // 16 bytes of an LDS row, 8-byte aligned
-    uint2 lo, hi;
-};
-
-__device__ __forceinline__ Frag lds_frag(const unsigned char* p) {
-    Frag f;
-    f.lo = *reinterpret_cast<const uint2*>(p);
-    f.hi = *reinterpret_cast<const uint2*>(p + 8);
-    return f;
-}
 
 // `rows` LDS rows from src rows row0 .. (pitch ld elements), the first `valid` of them exist;
 // channels k0 .. k0 + KC - 1, those >= C zero

@@ -1,14 +1,17 @@
-"""The closed set of the guard-band suite: which entries of include/ov3d.h the cases of
-tests/test_guard_*_gpu.py run between guard bands (read from each file's ENTRIES tuple, without
-importing it: no GPU needed), and which writing entries are not guarded yet, each with a
-one-line reason.  tests/test_guard_cpu.py checks that the two cover every entry that has a
-writable pointer parameter and that no name is in both."""
+"""The closed set of the guard-band suite: which entries of the headers (include/ov3d.h and the
+include/ov3d_*.h beside it) the cases of tests/test_guard_*_gpu.py and of the feature GPU files
+run between guard bands (read from each file's ENTRIES tuple, without importing it: no GPU
+needed), and which writing entries are not guarded yet, each with a one-line reason.
+tests/test_guard_cpu.py checks that the two cover every entry that has a writable pointer
+parameter and that no name is in both."""
 import ast
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 MODULES = ("test_guard_gemm_gpu", "test_guard_rows_gpu", "test_guard_attention_gpu",
-           "test_guard_points_gpu")
+           "test_guard_points_gpu", "test_lift_gpu", "test_lift_single_gpu", "test_box_eval_gpu",
+           "test_backproj_gpu", "test_pool_label_gpu", "test_open_vocab_gpu", "test_detect_gpu",
+           "test_nms_large_gpu", "test_label_vote_gpu")
 
 
 def path(module):
@@ -45,7 +48,7 @@ NOT_GUARDED = {
     **{n: _BN1 for n in ("ov3d_bn_finalize", "ov3d_bn_stats_finalize", "ov3d_bn_bwd_stats_finalize",
                          "ov3d_bn_bwd_finalize")},
     **{n: _GEOM for n in (
-        "ov3d_giou3d", "ov3d_giou3d_bwd", "ov3d_giou3d_bwd_aligned", "ov3d_hungarian", "ov3d_nms3d",
+        "ov3d_giou3d", "ov3d_giou3d_bwd", "ov3d_giou3d_bwd_aligned", "ov3d_hungarian",
         "ov3d_nms_boxes_from_corners", "ov3d_matcher_cost", "ov3d_targets_prep", "ov3d_set_loss_fwd",
         "ov3d_set_loss_fwd_split", "ov3d_set_loss_bwd", "ov3d_box_param_fwd", "ov3d_box_param_bwd",
         "ov3d_project_box2d", "ov3d_fourier_pe")},
@@ -56,8 +59,7 @@ NOT_GUARDED = {
     **{n: _LOADER for n in (
         "ov3d_sun_aug_points", "ov3d_sun_aug_boxes", "ov3d_sun_cuboid_eval", "ov3d_sun_crop_sample",
         "ov3d_sun_labels", "ov3d_scan_sample_aug", "ov3d_scan_labels", "ov3d_rows_gather")},
-    **{n: _EVAL for n in ("ov3d_box_points_count", "ov3d_box3d_iou_eval", "ov3d_ap_match",
-                          "ov3d_ap_curve")},
+    **{n: _EVAL for n in ("ov3d_box3d_iou_eval", "ov3d_ap_match", "ov3d_ap_curve")},
     "ov3d_adamw_step": "AdamW: one chunk table per tensor list; next after the tiled kernels",
     "ov3d_adamw_set_grads": "AdamW table setup (one pointer per tensor); next after the tiled kernels",
     "ov3d_multi_copy": "byte copies between caller-sized buffers; next after the tiled kernels",

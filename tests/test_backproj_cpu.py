@@ -142,11 +142,9 @@ def test_backproj_exports_are_the_header(ov3d):
     from ov3d_amd import _native, projection
     src = open(os.path.join(ROOT, "include", "ov3d_backproj.h")).read()
     protos = re.findall(r"^int\s+(ov3d_\w+)\(", src, flags=re.M)
-    assert set(_native.BACKPROJ_EXPORTS) == set(protos) == {
+    assert set(_native.HEADER_EXPORTS["ov3d_backproj.h"]) == set(protos) == {
         "ov3d_backproj_frames", "ov3d_backproj_tables", "ov3d_backproj_gather", "ov3d_backproj_compose"}
-    assert len(protos) == len(_native.BACKPROJ_EXPORTS)
-    assert not set(_native.BACKPROJ_EXPORTS) & (set(_native.EXPORTS) | set(_native.LIFT_EXPORTS)
-                                                | set(_native.BOXEVAL_EXPORTS))
+    assert len(protos) == len(_native.HEADER_EXPORTS["ov3d_backproj.h"])
     defines = dict(re.findall(r"^#define\s+(OV3D_BACKPROJ_\w+)\s+(\d+)", src, flags=re.M))
     assert (int(defines["OV3D_BACKPROJ_ROW"]), int(defines["OV3D_BACKPROJ_PARAMS"]),
             int(defines["OV3D_BACKPROJ_BLOCK"])) == (projection.ROW, projection.NPARAMS, projection.BLOCK) \

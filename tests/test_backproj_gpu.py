@@ -20,6 +20,9 @@ from test_backproj_cpu import PAR, gold, same
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_backproj_frames", "ov3d_backproj_tables", "ov3d_backproj_gather", "ov3d_backproj_compose")
+
 NS = (1, 63, 64, 65, 1023, 1024, 1025, 2500)
 FS = (1, 2, 5, 17)
 W, H = BC.IMAGE_DIMS

@@ -20,6 +20,9 @@ from test_box_eval_cpu import GOLD, check_metrics, same
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_boxeval_match", "ov3d_boxeval_tally")
+
 SCAN_P = (257, 0, 65, 1, 63, 64, 257, 65, 1)
 SCAN_G = (257, 256, 0, 255, 1, 257, 256, 255, 0)
 # S, T, C, ldp, ldg

@@ -30,10 +30,7 @@ def test_exports_are_the_header():
     with open(os.path.join(ROOT, "include", "ov3d_detect.h")) as f:
         text = f.read()
     protos = _native.read_header(text)[1]
-    assert set(_native.DETECT_EXPORTS) == set(protos) == {"ov3d_vocab_score"}
-    others = (_native.EXPORTS, _native.LIFT_EXPORTS, _native.BOXEVAL_EXPORTS, _native.BACKPROJ_EXPORTS,
-              _native.POOLLABEL_EXPORTS, _native.OPENVOCAB_EXPORTS, _native.LIFTVIEW_EXPORTS)
-    assert not any(set(_native.DETECT_EXPORTS) & set(o) for o in others)
+    assert set(_native.HEADER_EXPORTS["ov3d_detect.h"]) == set(protos) == {"ov3d_vocab_score"}
     lib = _native.load()
     for name, (restype, argtypes) in protos.items():
         fn = getattr(lib, name)

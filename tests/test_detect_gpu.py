@@ -36,6 +36,9 @@ from helpers import ov3d  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_vocab_score",)
+
 TILE = 256                      # OV3D_DETECT_TILE_T, the kernel's vocabulary tile width
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
 DT = list(DTYPES)

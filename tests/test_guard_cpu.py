@@ -172,11 +172,11 @@ def test_partially_written_outputs_and_rejections():
 
 
 def _writers():
-    """entries of include/ov3d.h with a pointer parameter that is not const-qualified (or a
+    """entries of the headers with a pointer parameter that is not const-qualified (or a
     pointer to a struct that carries such pointers): the ones that can write device memory"""
     from ov3d_amd import _native
-    text = open(_native.HEADER_PATH).read()
-    _, protos = _native.read_header(text)
+    text = "\n".join(open(p).read() for p in _native.HEADER_PATHS)
+    protos = _native.EXPORTS
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     structs = dict((name, body) for body, name in
                    re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S))
@@ -203,6 +203,7 @@ def test_every_writing_entry_is_guarded_or_listed():
     writers = _writers()
     assert {"ov3d_fps", "ov3d_gemm256", "ov3d_wgrad_group", "ov3d_lngemm_fwd", "ov3d_multi_copy",
             "ov3d_sun_labels", "ov3d_attn_bwd_dkdv_batch"} <= writers
+    assert {"ov3d_vocab_score", "ov3d_openvocab_classify", "ov3d_lift_nms", "ov3d_backproj_compose"} <= writers
     assert "ov3d_fps_workspace" not in writers and "ov3d_version" not in writers
     guarded = guard_cases.guarded()
     listed = set(guard_cases.NOT_GUARDED)

@@ -19,6 +19,9 @@ from test_pseudo_label_cpu import GOLD, check_files, product_formatter, same
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_box_points_count",)
+
 NS = (1, 63, 64, 65, 257, 1000)
 KS = (1, 7, 8, 9, 33)
 DTYPES = [pytest.param(np.float32, id="f32"), pytest.param(np.float64, id="f64")]

@@ -187,9 +187,10 @@ def test_entries_reject_invalid_arguments():
     """every entry of include/ov3d_lift.h validates before any launch (no device needed)"""
     from ov3d_amd import _native
     lib = _native.load()
-    assert set(_native.LIFT_EXPORTS) == {"ov3d_lift_frustum", "ov3d_lift_image", "ov3d_lift_nms",
-                                         "ov3d_lift_match"}
-    assert not set(_native.LIFT_EXPORTS) & set(_native.EXPORTS)
+    with open(os.path.join(ROOT, "include", "ov3d_lift.h")) as f:
+        protos = _native.read_header(f.read())[1]
+    assert set(_native.HEADER_EXPORTS["ov3d_lift.h"]) == set(protos) == {
+        "ov3d_lift_frustum", "ov3d_lift_image", "ov3d_lift_nms", "ov3d_lift_match"}
     p = ctypes.c_void_p(256)      # never dereferenced: every call below fails validation first
 
     ok = dict(pts=p, f64=1, N=4, labels=p, A=p, Ainv=p, planes=p, plabel=p, M=2, ws=p, lohi=p, ld=8, count=p)

@@ -20,6 +20,9 @@ from test_lift_single_cpu import GOLD, single_bar
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_liftview_frames",)
+
 SHAPES = [(1, 1), (3, 5), (7, 259), (240, 320)]
 SEG_VALUES = (0, 3, 17, 18, 25, -7, 39, 40, 4)
 

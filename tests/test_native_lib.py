@@ -1,5 +1,6 @@
-"""The C-ABI library: loads, exports every entry point include/ov3d.h declares,
-and the product refuses CPU tensors (no silent fallback).  No compute here."""
+"""The C-ABI library: loads, exports every entry point the headers (include/ov3d.h and the
+include/ov3d_*.h beside it) declare, and the product refuses CPU tensors (no silent fallback).
+No compute here."""
 import ctypes
 import os
 import re
@@ -12,9 +13,19 @@ import torch
 from helpers import ROOT, ov3d
 
 
+def header_sources():
+    """the text of every header the binding reads, include/ov3d.h first"""
+    from ov3d_amd import _native
+    assert _native.HEADER_PATHS[0] == _native.HEADER_PATH == os.path.join(ROOT, "include", "ov3d.h")
+    assert len(_native.HEADER_PATHS) >= 8
+    return [open(p).read() for p in _native.HEADER_PATHS]
+
+
 def header_symbols():
-    src = open(os.path.join(ROOT, "include", "ov3d.h")).read()
-    return sorted(set(re.findall(r"^(?:int|long long|const char\*)\s+(ov3d_\w+)\(", src, flags=re.M)))
+    found = [name for src in header_sources()
+             for name in re.findall(r"^(?:int|long long|const char\*)\s+(ov3d_\w+)\(", src, flags=re.M)]
+    assert len(found) == len(set(found))
+    return sorted(found)
 
 
 def test_library_exports_every_header_symbol():
@@ -61,8 +72,7 @@ def test_every_header_symbol_is_bound():
     argtypes of its parameter count; nothing is left to ctypes' int default"""
     from ov3d_amd import _native
     lib = _native.load()
-    src = open(os.path.join(ROOT, "include", "ov3d.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = "\n".join(re.sub(r"/\*.*?\*/", "", src, flags=re.S) for src in header_sources())
     protos = dict(re.findall(r"^(?:int|long long|const char\*)\s+(ov3d_\w+)\(([^)]*)\);", src, flags=re.M))
     assert sorted(protos) == header_symbols()
     assert set(protos) == set(_native.EXPORTS) and len(_native.EXPORTS) == len(protos)
@@ -84,7 +94,9 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     structs = re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S)
     assert len(structs) >= 10
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ov3d.h"', "int main(void) {"]
+    # the other headers have to compile as C beside it
+    lines = ["#include <stdio.h>", "#include <stddef.h>"]
+    lines += [f'#include "{os.path.basename(p)}"' for p in _native.HEADER_PATHS] + ["int main(void) {"]
     for body, name in structs:
         cls = _native.struct(name)
         assert cls is _native.struct(name)           # cached
@@ -130,11 +142,28 @@ def test_reader_rejects_types_outside_the_closed_set():
         _native.read_header("typedef struct { float w[OV3D_UNKNOWN]; } ov3d_v;\n")
 
 
-def test_missing_header_fails_loudly(monkeypatch):
+def test_missing_header_fails_loudly():
     from ov3d_amd import _native
-    monkeypatch.setattr(_native, "HEADER_PATH", "/nonexistent/ov3d.h")
     with pytest.raises(_native.NativeError, match="/nonexistent/ov3d.h"):
-        _native._read_own_header()
+        _native.read_headers(("/nonexistent/ov3d.h",) + _native.HEADER_PATHS[1:])
+
+
+def test_a_name_declared_in_two_headers_fails_loudly(tmp_path):
+    """entries and structs are unique across the headers: a second declaration would shadow the
+    first in the one binding table"""
+    from ov3d_amd import _native
+    a, b, c, d = (str(tmp_path / n) for n in ("ov3d.h", "ov3d_a.h", "ov3d_b.h", "ov3d_c.h"))
+    (tmp_path / "ov3d.h").write_text("typedef struct { int n; } ov3d_t;\nint ov3d_f(const ov3d_t* t);\n")
+    (tmp_path / "ov3d_a.h").write_text("int ov3d_g(int n);\nint ov3d_f(double x);\n")
+    (tmp_path / "ov3d_b.h").write_text("typedef struct { float w; } ov3d_t;\nint ov3d_h(int n);\n")
+    (tmp_path / "ov3d_c.h").write_text("typedef struct { float w; } ov3d_u;\nint ov3d_k(int n);\n")
+    structs, protos, exports = _native.read_headers((a, d))
+    assert set(structs) == {"ov3d_t", "ov3d_u"} and tuple(protos) == ("ov3d_f", "ov3d_k")
+    assert exports == {"ov3d.h": ("ov3d_f",), "ov3d_c.h": ("ov3d_k",)}
+    for other, name in ((b, "ov3d_f"), (c, "ov3d_t")):
+        with pytest.raises(_native.NativeError) as e:
+            _native.read_headers((a, other))
+        assert f"`{name}`" in str(e.value) and a in str(e.value) and other in str(e.value)
 
 
 def test_version_string():

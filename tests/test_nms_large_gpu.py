@@ -19,6 +19,9 @@ from ov3d_amd import nms
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_nms3d",)
+
 
 def _table(rs, B, K, levels=None):
     """(B, K, 8) boxes dense enough to suppress; scores from `levels` distinct values (ties)

@@ -18,6 +18,9 @@ from helpers import ov3d  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_openvocab_classify",)
+
 F_PLANES, P_PLANES = 3, 32 * 41
 DT = list(R.DTYPES)
 

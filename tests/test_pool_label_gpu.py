@@ -22,6 +22,9 @@ from test_pool_label_cpu import GOLD, SCAN, same
 
 pytestmark = pytest.mark.gpu
 
+# the entries this file's cases run between guard bands (tests/guard_cases.py)
+ENTRIES = ("ov3d_poollabel_vote", "ov3d_poollabel_confusion")
+
 BIG = np.finfo(np.float64).max
 # vertices per scan, boxes per scan, vertex dtype, row stride, min_label, bins
 VOTE_GROUPS = {

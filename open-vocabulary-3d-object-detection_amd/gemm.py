@@ -38,17 +38,40 @@ ROWS_GEMM = True
 ROWS_GEMM_MAX_M = int(os.environ.get("OV3D_ROWS_GEMM_MAX_M", "2048"))
 
 
+def _bf16_rows(t, dim=2):
+    """bf16 rows on the device with unit inner stride (all the weight-gradient kernels ask)"""
+    return t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == dim and t.stride(-1) == 1
+
+
+def _rows_ok(t):
+    """bf16 rows the GEMM kernels can load: 16-byte row segments (row stride % 8, aligned base)"""
+    return _bf16_rows(t) and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
+
+
+def _dims(a, w, trans_b):
+    """(M, N, K) of a (.., M, K) x w, or None when w's (.., N, K) (trans_b) / (.., K, N) does
+    not match"""
+    M, K = a.shape[-2:]
+    N, Kw = w.shape[-2:] if trans_b else (w.shape[-1], w.shape[-2])
+    return (M, N, K) if Kw == K else None
+
+
+def aligned_bias(b, align=2):
+    """b (or None) as a contiguous bf16 bias whose base is a multiple of `align` bytes; copied
+    only when it is not one already"""
+    if b is not None and (b.dtype != torch.bfloat16 or not b.is_contiguous() or b.data_ptr() % align):
+        b = b.to(torch.bfloat16).contiguous()
+        if b.data_ptr() % align:
+            b = b.clone()
+    return b
+
+
 def _rows_gemm_ok(a, w, trans_b):
-    if not (ROWS_GEMM and a.is_cuda and a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-            and a.dim() == 2 and w.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1):
+    if not (ROWS_GEMM and _rows_ok(a) and _rows_ok(w)):
         return False
-    M, K = a.shape
-    N = w.shape[0] if trans_b else w.shape[1]
-    if M > ROWS_GEMM_MAX_M or (w.shape[1] if trans_b else w.shape[0]) != K:
-        return False
-    if a.data_ptr() % 16 or w.data_ptr() % 16 or a.stride(0) % 8 or w.stride(0) % 8:
-        return False
-    return bool(_native.load().ov3d_rows_gemm_supported(M, N, K))
+    mnk = _dims(a, w, trans_b)
+    return (mnk is not None and mnk[0] <= ROWS_GEMM_MAX_M
+            and bool(_native.load().ov3d_rows_gemm_supported(*mnk)))
 
 
 def rows_gemm(a, w, bias=None, trans_b=True):
@@ -57,10 +80,8 @@ def rows_gemm(a, w, bias=None, trans_b=True):
     M, K = a.shape
     N = w.shape[0] if trans_b else w.shape[1]
     out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    if bias is not None and (bias.dtype != torch.bfloat16 or not bias.is_contiguous()):
-        bias = bias.to(torch.bfloat16).contiguous()
-    _native.call("ov3d_rows_gemm", M, N, K, a, a.stride(0), w, w.stride(0), int(trans_b), bias,
-                 out, N, like=a)
+    _native.call("ov3d_rows_gemm", M, N, K, a, a.stride(0), w, w.stride(0), int(trans_b),
+                 aligned_bias(bias), out, N, like=a)
     return out
 
 
@@ -76,8 +97,7 @@ def rows_gemm_group(problems, trans_b=True):
     for a, w, b in problems:
         N = w.shape[0] if trans_b else w.shape[1]
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-        if b is not None and (b.dtype != torch.bfloat16 or not b.is_contiguous()):
-            b = b.to(torch.bfloat16).contiguous()
+        b = aligned_bias(b)
         keep.append(b)
         outs.append(out)
         probs.append(_RgProblem(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0),
@@ -97,6 +117,14 @@ def _group_ok(pairs, trans_b):
             and all(_rows_gemm_ok(a, w, trans_b) for a, w in pairs))
 
 
+def dgrad_blocks(pairs):
+    """[(dy, w)] -> [dy @ w], the input gradients of several row blocks: one rows_gemm_group
+    launch when _group_ok, else one _dgrad each"""
+    if _group_ok(pairs, False):
+        return rows_gemm_group([(dy, w, None) for dy, w in pairs], trans_b=False)
+    return [_dgrad(dy, w) for dy, w in pairs]
+
+
 # Long row blocks (the encoder: batch * 2048 rows, the heads: batch * 1024) run on
 # csrc/tilegemm.hip: persistent 64- / 128-row tiles, both operands double-buffered in LDS, the
 # FFN activation as an epilogue (DESIGN.md "Long row-block GEMMs").  OV3D_TILE_GEMM=0: hipBLASLt.
@@ -104,28 +132,23 @@ TILE_GEMM = os.environ.get("OV3D_TILE_GEMM", "1") == "1"
 
 
 def _tile_gemm_ok(a, w, trans_b):
-    if not (TILE_GEMM and a.is_cuda and a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-            and a.dim() == 2 and w.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1):
+    if not (TILE_GEMM and _rows_ok(a) and _rows_ok(w)):
         return False
-    M, K = a.shape
-    N = w.shape[0] if trans_b else w.shape[1]
-    if M <= ROWS_GEMM_MAX_M or (w.shape[1] if trans_b else w.shape[0]) != K:
-        return False
-    if a.data_ptr() % 16 or w.data_ptr() % 16 or a.stride(0) % 8 or w.stride(0) % 8:
-        return False
-    return bool(_native.load().ov3d_tile_gemm_supported(M, N, K))
+    mnk = _dims(a, w, trans_b)
+    return (mnk is not None and mnk[0] > ROWS_GEMM_MAX_M
+            and bool(_native.load().ov3d_tile_gemm_supported(*mnk)))
 
 
-def tile_gemm(a, w, bias=None, trans_b=True, out=None):
-    """as rows_gemm, on the long row-block kernel (check _tile_gemm_ok first); `out` an (M, N)
-    bf16 row view (stride(1) == 1, 16-byte aligned, row stride % 8 == 0) or None"""
+tile_out_ok = _rows_ok   # an `out` row view tile_gemm can write
+
+
+def _tile_gemm(a, w, bias=None, trans_b=True, out=None):
+    """as rows_gemm, on the long row-block kernel (check _tile_gemm_ok, and _rows_ok(out), first)"""
     M, K = a.shape
     N = w.shape[0] if trans_b else w.shape[1]
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    if bias is not None and (bias.dtype != torch.bfloat16 or not bias.is_contiguous()
-                             or bias.data_ptr() % 8):   # 8-byte bias pieces
-        bias = bias.to(torch.bfloat16).contiguous().clone()
+    bias = aligned_bias(bias, 8)           # 8-byte bias pieces
     wide = bias is not None and N > 2048   # the kernel stages the bias row in LDS (N <= 2048)
     _native.call("ov3d_tile_gemm", M, N, K, a, a.stride(0), w, w.stride(0), int(trans_b),
                  None if wide else bias, out, out.stride(0), like=a)
@@ -134,40 +157,38 @@ def tile_gemm(a, w, bias=None, trans_b=True, out=None):
     return out
 
 
-def tile_out_ok(out):
-    return (out.dtype == torch.bfloat16 and out.dim() == 2 and out.stride(1) == 1
-            and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0)
+def tile_gemm(a, w, bias=None, trans_b=True, out=None):
+    """a w^T (trans_b) / a w (+ bias) on the long row-block kernel when it applies, else the
+    library product; `out`: an (M, N) bf16 row view to write, or None"""
+    if _tile_gemm_ok(a, w, trans_b) and (out is None or _rows_ok(out)):
+        return _tile_gemm(a, w, bias, trans_b, out)
+    y = torch.mm(a, w.t() if trans_b else w, out=out)
+    return y if bias is None else y.add_(bias)
 
 
 def tile_bmm_ok(a, w, trans_b):
     """a (B, M, K) x w (B, N, K) (trans_b) / (B, K, N) on the long row-block kernel"""
-    if not (TILE_GEMM and a.is_cuda and a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-            and a.dim() == 3 and w.dim() == 3 and a.shape[0] == w.shape[0]
-            and a.stride(2) == 1 and w.stride(2) == 1):
+    if not (TILE_GEMM and _bf16_rows(a, 3) and _bf16_rows(w, 3) and a.shape[0] == w.shape[0]):
         return False
-    B, M, K = a.shape
-    N = w.shape[1] if trans_b else w.shape[2]
-    if M <= ROWS_GEMM_MAX_M or (w.shape[2] if trans_b else w.shape[1]) != K:
+    mnk = _dims(a, w, trans_b)
+    if mnk is None or mnk[0] <= ROWS_GEMM_MAX_M:
         return False
     if (a.data_ptr() % 16 or w.data_ptr() % 16 or any(x % 8 for x in a.stride()[:2] + w.stride()[:2])):
         return False
-    return bool(_native.load().ov3d_tile_gemm_supported(M, N, K))
+    return bool(_native.load().ov3d_tile_gemm_supported(*mnk))
 
 
 def tile_bmm(a, w, trans_b):
-    """torch.bmm(a, w.transpose(1, 2) if trans_b else w) -> (B, M, N) bf16, one launch"""
+    """torch.bmm(a, w.transpose(1, 2) if trans_b else w) -> (B, M, N) bf16: one launch of the
+    long row-block kernel when tile_bmm_ok, else the library product"""
+    if not tile_bmm_ok(a, w, trans_b):
+        return torch.bmm(a, w.transpose(1, 2) if trans_b else w)
     B, M, K = a.shape
     N = w.shape[1] if trans_b else w.shape[2]
     out = torch.empty((B, M, N), dtype=torch.bfloat16, device=a.device)
     _native.call("ov3d_tile_gemm_batched", B, M, N, K, a, a.stride(1), a.stride(0), w, w.stride(1),
                  w.stride(0), int(trans_b), out, N, M * N, like=a)
     return out
-
-
-def _aligned_bias(b):
-    if b is not None and (b.dtype != torch.bfloat16 or not b.is_contiguous() or b.data_ptr() % 8):
-        b = b.to(torch.bfloat16).contiguous().clone()
-    return b
 
 
 def shape_ok(M, N, K):
@@ -191,7 +212,7 @@ def act_gemm(a, w, bias=None, trans_b=True, epilogue=0, p=0.0, seed=None, site=0
     N = w.shape[0] if trans_b else w.shape[1]
     out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
     name = "ov3d_rows_gemm_act" if _rows_gemm_ok(a, w, trans_b) else "ov3d_tile_gemm_act"
-    _native.call(name, M, N, K, a, a.stride(0), w, w.stride(0), int(trans_b), _aligned_bias(bias),
+    _native.call(name, M, N, K, a, a.stride(0), w, w.stride(0), int(trans_b), aligned_bias(bias, 8),
                  int(epilogue), float(p), seed, int(site), h, h.stride(0) if h is not None else 0,
                  out, N, like=a)
     return out
@@ -209,13 +230,10 @@ def tile_gemm2(a1, w1, a2, w2):
 
 # Large products (the RegionCLIP res5 convolutions over all ROIs, the decoder's memory K / V
 # projections): 256 x 256 tiles on csrc/gemm256.hip, bias / residual / ReLU in the epilogue,
-# and the 3x3 convolution as an implicit GEMM (no column matrix).  OV3D_GEMM256=0: hipBLASLt.
+# and the 3x3 convolution as an implicit GEMM (no column matrix).  OV3D_GEMM256=0: the row-block
+# kernels or hipBLASLt for the linear layers here; the RegionCLIP bf16 convolutions have no other
+# backend and raise (regionclip._conv1x1).
 GEMM256 = os.environ.get("OV3D_GEMM256", "1") == "1"
-
-
-def _rows_ok(t):
-    return (t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0
-            and t.data_ptr() % 16 == 0 and t.is_cuda)
 
 
 def gemm256_ok(a, w, residual=None, out=None):
@@ -237,10 +255,7 @@ def _bias_arg(bias):
     if bias.dtype == torch.float32:
         b = bias if bias.is_contiguous() and bias.data_ptr() % 16 == 0 else bias.contiguous().clone()
         return b, 1
-    b = bias.to(torch.bfloat16)
-    if not b.is_contiguous() or b.data_ptr() % 16:
-        b = b.contiguous().clone()
-    return b, 0
+    return aligned_bias(bias, 16), 0
 
 
 def gemm256(a, w, bias=None, residual=None, relu=False, out=None):
@@ -353,50 +368,36 @@ def _linear(x, w, b):
     on tilegemm, the longest on rows256 (256 x 256 weights) or gemm256"""
     if _rows_gemm_ok(x, w, True):
         return rows_gemm(x, w, b, trans_b=True)
-    if x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and rows256_ok(x, w, b):
+    if rows256_ok(x, w, b):
         return rows256(x, w)
-    if x.shape[0] >= GEMM256_MIN_M and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 \
-            and gemm256_ok(x, w):
+    tile = _tile_gemm_ok(x, w, True)
+    # gemm256: the longest row blocks, and the shorter ones tilegemm does not take (K % 64 != 0:
+    # the masked encoder's interim SA, 256 features + xyz padded to 264)
+    if (x.shape[0] >= GEMM256_MIN_M or not tile) and gemm256_ok(x, w):
         return gemm256(x, w, bias=b)
-    if _tile_gemm_ok(x, w, True):
-        return tile_gemm(x, w, b, trans_b=True)
-    if x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and gemm256_ok(x, w):
-        # K % 64 != 0 (the masked encoder's interim SA: 256 features + xyz padded to 264)
-        return gemm256(x, w, bias=b)
+    if tile:
+        return _tile_gemm(x, w, b, trans_b=True)
     return torch.nn.functional.linear(x, w, b)
-
-
-def linear_weight_grads(dy, xc, w, b, need_w, need_b):
-    """(dW, db) of y = xc w^T + b for the gradient dy (bf16 rows like xc), or (None, None)
-    when they were queued for the grouped launch at the end of the backward (DEFER_WGRAD)"""
-    want_b = b is not None and need_b
-    if need_w and can_defer(xc, w, b if want_b else None):
-        defer_weight_grad(dy, xc, w, b if want_b else None)
-        return None, None
-    if need_w and _fused_ok(dy, xc):
-        dw, db = fused_weight_grad(dy, xc, bias=want_b)
-        return dw.to(w.dtype), (db.to(b.dtype) if want_b else None)
-    dw = weight_grad(dy, xc).to(w.dtype) if need_w else None
-    db = torch.sum(dy, dim=0, dtype=torch.float32).to(b.dtype) if want_b else None
-    return dw, db
 
 
 def _dgrad(dy, w):
     """dy (M, N) @ w (N, K) for the input gradient of a linear layer"""
     if _rows_gemm_ok(dy, w, False):
         return rows_gemm(dy, w, trans_b=False)
-    if dy.shape[0] >= GEMM256_MIN_M and dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16:
-        wt = w.t().contiguous()   # (K, N) rows: dx = dy wt^T on the 256 x 256 tile kernel
+    M = dy.shape[0]
+    tile = _tile_gemm_ok(dy, w, False)
+    # rows256 / gemm256 take (K, N) rows, dx = dy wt^T: the longest row blocks, and those above
+    # ROWS_GEMM_MAX_M tilegemm does not take.  The transpose is a launch of its own, so it is
+    # formed for bf16 operands on these two routes only
+    if dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and \
+            (M >= GEMM256_MIN_M or (not tile and M > ROWS_GEMM_MAX_M)):
+        wt = w.t().contiguous()
         if rows256_ok(dy, wt):
             return rows256(dy, wt)
         if gemm256_ok(dy, wt):
             return gemm256(dy, wt)
-    if _tile_gemm_ok(dy, w, False):
-        return tile_gemm(dy, w, trans_b=False)
-    if dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and dy.shape[0] > ROWS_GEMM_MAX_M:
-        wt = w.t().contiguous()   # (K, N) rows: dx = dy wt^T on the tile kernel
-        if gemm256_ok(dy, wt):
-            return gemm256(dy, wt)
+    if tile:
+        return _tile_gemm(dy, w, trans_b=False)
     return dy @ w
 
 
@@ -439,9 +440,9 @@ def _wg_group_splits(R):
 
 
 def _fused_ok(dy, x):
-    """the one-launch HIP weight/bias gradient applies to bf16 rows on the ROCm device"""
-    return (dy.is_cuda and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-            and dy.dim() == 2 and x.dim() == 2 and dy.stride(1) == 1 and x.stride(1) == 1)
+    """the one-launch HIP weight/bias gradient applies to bf16 rows on the ROCm device (any row
+    stride and base: csrc/wgrad.hip loads unaligned rows per element)"""
+    return _bf16_rows(dy) and _bf16_rows(x)
 
 
 def fused_weight_grad(dy, x, bias=True, out_w=None, out_b=None, bn=None):
@@ -556,8 +557,7 @@ def _leaf_param(w):
 
 def can_defer(x, w, b=None):
     """x: the saved bf16 input rows (dy is cast to x's dtype and made row-contiguous)"""
-    return (DEFER_WGRAD and not torch.is_grad_enabled() and x.is_cuda
-            and x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1
+    return (DEFER_WGRAD and not torch.is_grad_enabled() and _bf16_rows(x)
             and _leaf_param(w) is not None and (b is None or _leaf_param(b) is not None))
 
 
@@ -646,6 +646,43 @@ def weight_grad(dy, x, out=None):
     return torch.sum(part, dim=0, dtype=torch.float32, out=out)
 
 
+def weight_grads(blocks, w, b, need_w, need_b):
+    """(dW, db) of the parameter w (rows, Cin) and its bias b (or None) from blocks
+    [(dy, x, rows, bn)]: dy (R, n) the bf16 output gradient and x (R, Cin) the bf16 input rows of
+    y = x w[r0:r1]^T + b[r0:r1], rows = (r0, r1) or None for the whole parameter, bn =
+    (scale, shift) or None as in fused_weight_grad.  The one policy of every linear layer:
+    queued for the grouped launch at the end of the backward when every block can be
+    (DEFER_WGRAD; -> (None, None)), else each block written straight into its rows of ONE fp32
+    gradient (rows no block covers are zero) by the one-launch kernel, or by the split-K library
+    product + column sums where that does not apply.  db without dW is still computed."""
+    bq = b if (b is not None and need_b) else None   # the bias whose gradient is wanted
+    if need_w and all(can_defer(x, w, bq) for _, x, _, _ in blocks):
+        for dy, x, rows, bn in blocks:
+            defer_weight_grad(dy, x, w, bq, rows=rows, bn=bn)
+        return None, None
+    covered = sum(w.shape[0] if rows is None else rows[1] - rows[0] for _, _, rows, _ in blocks)
+    alloc = torch.empty if covered == w.shape[0] else torch.zeros
+    dw = alloc(w.shape, dtype=torch.float32, device=w.device) if need_w else None
+    db = alloc(bq.shape, dtype=torch.float32, device=w.device) if bq is not None else None
+    for dy, x, rows, bn in blocks:
+        r = slice(None) if rows is None else slice(*rows)
+        if dw is not None and (bn is not None or _fused_ok(dy, x)):   # bn: on that kernel only
+            fused_weight_grad(dy, x, bias=db is not None, out_w=dw[r],
+                              out_b=db[r] if db is not None else None, bn=bn)
+            continue
+        if dw is not None:
+            weight_grad(dy, x, out=dw[r])
+        if db is not None:
+            torch.sum(dy, dim=0, dtype=torch.float32, out=db[r])
+    return (dw.to(w.dtype) if dw is not None else None,
+            db.to(b.dtype) if db is not None else None)
+
+
+def linear_weight_grads(dy, x, w, b, need_w, need_b):
+    """weight_grads of a whole layer y = x w^T + b"""
+    return weight_grads([(dy, x, None, None)], w, b, need_w, need_b)
+
+
 # bf16 copies of the fp32 parameters used under autocast.  Casting per call costs a kernel
 # per weight and bias per step (~300 launches); instead every stale copy is refreshed with
 # ONE multi-tensor copy the first time a parameter changed by the optimizer (its version
@@ -731,29 +768,18 @@ class _RowsLinear(Function):
         with torch.autocast("cuda", enabled=False):
             y = _linear(xc, wc, cast_param(b, dt))   # bias in the GEMM epilogue
         ctx.save_for_backward(xc, wc)
-        ctx.meta = (x.dtype, w.dtype, b is not None)
+        ctx.xdt = x.dtype
         ctx.params = (w, b)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         xc, wc = ctx.saved_tensors
-        xdt, wdt, has_b = ctx.meta
         dy = dy.to(xc.dtype).contiguous()
         with torch.autocast("cuda", enabled=False):
-            dx = _dgrad(dy, wc).to(xdt) if ctx.needs_input_grad[0] else None
-            want_b = has_b and ctx.needs_input_grad[2]
-            w, b = ctx.params
-            if ctx.needs_input_grad[1] and can_defer(xc, w, b if want_b else None):
-                defer_weight_grad(dy, xc, w, b if want_b else None)
-                return dx, None, None
-            if ctx.needs_input_grad[1] and _fused_ok(dy, xc):
-                dw, db = fused_weight_grad(dy, xc, bias=want_b)
-                dw = dw.to(wdt)
-                db = db.to(wdt) if want_b else None
-            else:
-                dw = weight_grad(dy, xc).to(wdt) if ctx.needs_input_grad[1] else None
-                db = torch.sum(dy, dim=0, dtype=torch.float32).to(wdt) if want_b else None
+            dx = _dgrad(dy, wc).to(ctx.xdt) if ctx.needs_input_grad[0] else None
+            dw, db = linear_weight_grads(dy, xc, *ctx.params, ctx.needs_input_grad[1],
+                                         ctx.needs_input_grad[2])
         return dx, dw, db
 
 
@@ -828,56 +854,26 @@ class _InProj(Function):
                 outs.append(y.view(*x.shape[:-1], r1 - r0))
                 saved.append(xc)
         ctx.save_for_backward(wc, *saved)
-        ctx.meta = (spec, w.dtype, b is not None, tuple(x.dtype for x in xs),
-                    tuple(x.shape for x in xs))
+        ctx.meta = (spec, tuple(x.dtype for x in xs), tuple(x.shape for x in xs))
         ctx.params = (w, b)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dys):
         wc, *xcs = ctx.saved_tensors
-        spec, wdt, has_b, xdts, xshapes = ctx.meta
-        wp, bp = ctx.params
-        want_b = has_b and ctx.needs_input_grad[1]
-        defer = ctx.needs_input_grad[0] and all(can_defer(xc, wp, bp if want_b else None)
-                                                for xc in xcs)
-        full = sum(r1 - r0 for r0, r1 in spec) == wc.shape[0]   # else zero the other rows
-        alloc = torch.empty if full else torch.zeros
-        dw = alloc(wc.shape, dtype=torch.float32, device=wc.device) \
-            if ctx.needs_input_grad[0] and not defer else None
-        db = alloc(wc.shape[0], dtype=torch.float32, device=wc.device) \
-            if want_b and not defer else None
-        dxs = []
+        spec, xdts, xshapes = ctx.meta
         with torch.autocast("cuda", enabled=False):
             dys = [(torch.zeros(xc.shape[0], r1 - r0, dtype=xc.dtype, device=xc.device)
                     if dy is None else dy.reshape(-1, r1 - r0).to(xc.dtype).contiguous())
                    for dy, xc, (r0, r1) in zip(dys, xcs, spec)]
             want = [i for i in range(len(dys)) if ctx.needs_input_grad[3 + i]]
+            dxs = [None] * len(dys)
             pairs = [(dys[i], wc[spec[i][0]:spec[i][1]]) for i in want]
-            dx_all = [None] * len(dys)
-            if _group_ok(pairs, False):   # the input gradients in one launch
-                for i, d in zip(want, rows_gemm_group([(a, w, None) for a, w in pairs],
-                                                      trans_b=False)):
-                    dx_all[i] = d
-            for i, (dy, xc, (r0, r1)) in enumerate(zip(dys, xcs, spec)):
-                if ctx.needs_input_grad[3 + i]:
-                    d = dx_all[i] if dx_all[i] is not None else _dgrad(dy, wc[r0:r1])
-                    dxs.append(d.to(xdts[i]).view(xshapes[i]))
-                else:
-                    dxs.append(None)
-                if defer:
-                    defer_weight_grad(dy, xc, wp, bp if want_b else None, rows=(r0, r1))
-                    continue
-                if dw is not None and _fused_ok(dy, xc):
-                    fused_weight_grad(dy, xc, bias=db is not None, out_w=dw[r0:r1],
-                                      out_b=db[r0:r1] if db is not None else None)
-                    continue
-                if dw is not None:
-                    weight_grad(dy, xc, out=dw[r0:r1])
-                if db is not None:
-                    torch.sum(dy, dim=0, dtype=torch.float32, out=db[r0:r1])
-        return (dw.to(wdt) if dw is not None else None,
-                db.to(wdt) if db is not None else None, None, *dxs)
+            for i, d in zip(want, dgrad_blocks(pairs)):
+                dxs[i] = d.to(xdts[i]).view(xshapes[i])
+            dw, db = weight_grads([(dy, xc, rows, None) for dy, xc, rows in zip(dys, xcs, spec)],
+                                  *ctx.params, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return (dw, db, None, *dxs)
 
 
 def in_projection(w, b, groups):

@@ -285,7 +285,7 @@ class _RowsLinearMask(torch.autograd.Function):
         hr = h.reshape(-1, h.shape[-1])
         wc, bc = gemm.cast_param(w, bf), gemm.cast_param(b, bf)
         with torch.autocast("cuda", enabled=False):
-            y = gemm.act_gemm(hr, wc, _bias(bc), True)
+            y = gemm.act_gemm(hr, wc, bc, True)
         ctx.save_for_backward(hr, wc)
         ctx.params = (w, b)
         ctx.meta = (h.shape, float(relu_p))
@@ -335,7 +335,7 @@ class _LnGemm(torch.autograd.Function):
         if lin:
             yr = yx.reshape(-1, yx.shape[-1])
             with torch.autocast("cuda", enabled=False):
-                y = gemm.act_gemm(yr, ywc, _bias(gemm.cast_param(yb, bf)), True)
+                y = gemm.act_gemm(yr, ywc, gemm.cast_param(yb, bf), True)
         else:
             yr = None
             y = _rows(yx, C).to(bf).contiguous() if yx is not None else None
@@ -402,18 +402,15 @@ class _LnGemm(torch.autograd.Function):
         with torch.autocast("cuda", enabled=False):
             d = [dd.reshape(R, -1).to(bf).contiguous() if dd is not None else None for dd in douts]
             # the linear's input gradients: dxa (sel 0 problems), dxap (sel 1), one launch
-            pairs = [(d[i], gwc[r0:r1], sel) for i, (sel, r0, r1) in enumerate(spec)
-                     if d[i] is not None]
+            live = [(d[i], sel, r0, r1) for i, (sel, r0, r1) in enumerate(spec) if d[i] is not None]
+            pairs = [(dd, gwc[r0:r1]) for dd, _, r0, r1 in live]
+            sels = [sel for _, sel, _, _ in live]
+            # two problems that read the same input add into it: each on its own launch then
+            dxs = gemm.dgrad_blocks(pairs) if len(set(sels)) == len(sels) else \
+                [gemm._dgrad(a, w) for a, w in pairs]
             dsel = {0: None, 1: None}
-            if len(pairs) > 1 and gemm._group_ok([(a, w) for a, w, _ in pairs], False) and \
-                    len({sel for _, _, sel in pairs}) == len(pairs):
-                for (_, _, sel), o in zip(pairs, gemm.rows_gemm_group(
-                        [(a, w, None) for a, w, _ in pairs], trans_b=False)):
-                    dsel[sel] = o
-            else:
-                for a, w, sel in pairs:
-                    o = gemm._dgrad(a, w)
-                    dsel[sel] = o if dsel[sel] is None else dsel[sel] + o
+            for sel, o in zip(sels, dxs):
+                dsel[sel] = o if dsel[sel] is None else dsel[sel] + o
             lin = ywc is not None
             need_y = lin and (nig[2] or nig[3] or nig[4])
             need = (False, nig[1], need_y or (not lin and nig[2]), nig[5], nig[6], nig[7], nig[8],
@@ -441,31 +438,9 @@ class _LnGemm(torch.autograd.Function):
             else:
                 dyx = dy
             # the linear's weight / bias gradients (row blocks of one weight, as _InProj)
-            dgw = dgbias = None
-            want_b = gbias is not None and nig[11]
-            if nig[10] or want_b:
-                items = [(d[i], xap if sel == 1 else xa, (r0, r1))
-                         for i, (sel, r0, r1) in enumerate(spec) if d[i] is not None]
-                if nig[10] and all(gemm.can_defer(x, gw, gbias if want_b else None)
-                                   for _, x, _ in items):
-                    for dd, x, rows in items:
-                        gemm.defer_weight_grad(dd, x, gw, gbias if want_b else None, rows=rows)
-                else:
-                    dgw = torch.zeros(gw.shape, dtype=torch.float32, device=dev) if nig[10] else None
-                    dgbias = torch.zeros(gbias.shape, dtype=torch.float32, device=dev) \
-                        if want_b else None
-                    for dd, x, (r0, r1) in items:
-                        if dgw is not None and gemm._fused_ok(dd, x):
-                            gemm.fused_weight_grad(dd, x, bias=dgbias is not None,
-                                                   out_w=dgw[r0:r1],
-                                                   out_b=dgbias[r0:r1] if dgbias is not None else None)
-                            continue
-                        if dgw is not None:
-                            gemm.weight_grad(dd, x, out=dgw[r0:r1])
-                        if dgbias is not None:
-                            torch.sum(dd, dim=0, dtype=torch.float32, out=dgbias[r0:r1])
-                    dgw = dgw.to(gw.dtype) if dgw is not None else None
-                    dgbias = dgbias.to(gbias.dtype) if dgbias is not None else None
+            dgw, dgbias = gemm.weight_grads(
+                [(dd, xap if sel == 1 else xa, (r0, r1), None) for dd, sel, r0, r1 in live],
+                gw, gbias, nig[10], nig[11])
         return (None, dsrc, dyx, dyw, dyb, dpos, dga, dba, dgb, dbb, dgw, dgbias)
 
 
@@ -631,8 +606,8 @@ class _FFN(torch.autograd.Function):
         w2c, b2c = gemm.cast_param(w2, bf), gemm.cast_param(b2, bf)
         M, F, N = xc.shape[0], w1c.shape[0], w2c.shape[0]
         seed = flash._seed(x.device) if p > 0 else None
-        h = gemm.act_gemm(xc, w1c, _bias(b1c), True, 1, p, seed, site)
-        y = gemm.act_gemm(h, w2c, _bias(b2c), True)
+        h = gemm.act_gemm(xc, w1c, b1c, True, 1, p, seed, site)
+        y = gemm.act_gemm(h, w2c, b2c, True)
         ctx.save_for_backward(xc, h, w1c, w2c)
         ctx.params = (w1, b1, w2, b2)
         ctx.meta = (float(p), x.shape, x.dtype)
@@ -653,10 +628,6 @@ class _FFN(torch.autograd.Function):
         return dx, dw1, db1, dw2, db2, None, None
 
 
-def _bias(b):
-    return b.contiguous() if b is not None else None
-
-
 # The encoder layer's chain after its self-attention (out-projection, residual + dropout, norm2,
 # linear1 -> ReLU -> dropout -> linear2) in one launch each way (csrc/encpost.hip).
 # OV3D_ENC_POST=0: the four launches each way; "fwd" / "bwd": only that direction fused.
@@ -664,10 +635,6 @@ _ENC_POST = os.environ.get("OV3D_ENC_POST", "1")
 enc_post = _ENC_POST != "0"
 enc_post_fwd = _ENC_POST != "bwd"   # with enc_post: the forward on ov3d_enc_post_fwd
 enc_post_bwd = _ENC_POST != "fwd"   # with enc_post: the backward on ov3d_enc_post_bwd
-
-
-def _al16(t):
-    return t if (t.is_contiguous() and t.data_ptr() % 16 == 0) else t.contiguous().clone()
 
 
 class _EncPost(torch.autograd.Function):
@@ -688,7 +655,7 @@ class _EncPost(torch.autograd.Function):
         R = sr.shape[0]
         dev = sr.device
         woc, w1c, w2c = gemm.cast_param(wo, bf), gemm.cast_param(w1, bf), gemm.cast_param(w2, bf)
-        boc, b1c, b2c = (_al16(gemm.cast_param(b, bf)) for b in (bo, b1, b2))
+        boc, b1c, b2c = (gemm.aligned_bias(gemm.cast_param(b, bf), 16) for b in (bo, b1, b2))
         F = w1c.shape[0]
         kq = int(gemm.ROWS_GEMM and R <= gemm.ROWS_GEMM_MAX_M)
         seed = flash._seed(dev) if (p1 > 0 or pf > 0) else None
@@ -815,8 +782,8 @@ def ffn_weights_ok(x, w1, w2):
     xr = x.reshape(-1, x.shape[-1])
     bf = torch.bfloat16
     w1c, w2c = gemm.cast_param(w1, bf), gemm.cast_param(w2, bf)
-    if not (gemm.act_gemm_ok(xr, w1c, True) and w2c.stride(1) == 1 and w2c.stride(0) % 8 == 0
-            and w2c.data_ptr() % 16 == 0 and w2c.shape[1] == w1c.shape[0]):
+    if not (gemm.act_gemm_ok(xr, w1c, True) and gemm._rows_ok(w2c)
+            and w2c.shape[1] == w1c.shape[0]):
         return False
     # the launches on the fresh (contiguous) h / dy / dy1 rows: linear2, its input gradient
     # (output F columns over N), linear1's input gradient (C columns over F); the short

@@ -191,20 +191,12 @@ class _MemoryKV(torch.autograd.Function):
                 dmk = dK @ Wk
                 # in place when dmk is not also pos's gradient (no copy of dmk into a new output)
                 dmem = dmk.addmm_(dV, Wv) if not pos_grad else dV @ Wv + dmk
-            grads = [None] * len(params)
-            for l in range(L):
-                w, b = params[2 * l], params[2 * l + 1]
-                for blk, (dy, x) in enumerate(((dK, mpos), (dV, mem))):
-                    r0 = (1 + blk) * E
-                    dyl = dy[:, l * E:(l + 1) * E]
-                    if gemm.can_defer(x, w, b):
-                        gemm.defer_weight_grad(dyl, x, w, b, rows=(r0, r0 + E))
-                        continue
-                    if grads[2 * l] is None:
-                        grads[2 * l] = torch.zeros(w.shape, dtype=torch.float32, device=w.device)
-                        grads[2 * l + 1] = torch.zeros(b.shape, dtype=torch.float32, device=b.device)
-                    gemm.fused_weight_grad(dyl, x, bias=True, out_w=grads[2 * l][r0:r0 + E],
-                                           out_b=grads[2 * l + 1][r0:r0 + E])
+            grads = []
+            for l in range(L):   # the K and V row blocks of layer l's in_proj weight / bias
+                cols = slice(l * E, (l + 1) * E)
+                grads += gemm.weight_grads([(dK[:, cols], mpos, (E, 2 * E), None),
+                                            (dV[:, cols], mem, (2 * E, 3 * E), None)],
+                                           params[2 * l], params[2 * l + 1], True, True)
         shape = ctx.bufs[0].shape[:2] + (C,)
         dpos = dmk.view(shape).to(mdt) if pos_grad else None
         return (dmem.view(shape).to(mdt), dpos, None, *grads)

@@ -16,10 +16,10 @@
 //      and refreshes the parameter's bf16 copy used by the autocast GEMMs (gemm.py).
 // Coalesced fp32 element streams; HBM-bound (28 B per parameter, + 2 B with a shadow).
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef __bf16 bf16;
 constexpr int kThreads = 256;
 constexpr int kPer = 16;                 // elements per thread
 constexpr int kChunk = kThreads * kPer;  // elements per workgroup
@@ -213,7 +213,6 @@ extern "C" int ov3d_seed_next(long long* live, long long* snap, void* stream) {
 // into a bf16 output; a fp32 or bf16, b fp32) and ac = bf16(a) for a fp32 (NULL: skipped), 8
 // elements a thread (the add was a mixed-type torch launch, the cast another)
 namespace {
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 template <bool ABF16>
 __global__ void __launch_bounds__(256) add_cast_kernel(const void* __restrict__ a,
                                                        const float* __restrict__ b, long long n8,
@@ -222,7 +221,7 @@ __global__ void __launch_bounds__(256) add_cast_kernel(const void* __restrict__ 
     if (i >= n8) return;
     float av[8];
     if (ABF16) {
-        const bf16x8_t a8 = reinterpret_cast<const bf16x8_t*>(a)[i];
+        const bf16x8 a8 = reinterpret_cast<const bf16x8*>(a)[i];
 #pragma unroll
         for (int j = 0; j < 8; ++j) av[j] = (float)a8[j];
     } else {
@@ -234,14 +233,14 @@ __global__ void __launch_bounds__(256) add_cast_kernel(const void* __restrict__ 
     const float4 b0 = reinterpret_cast<const float4*>(b)[2 * i];
     const float4 b1 = reinterpret_cast<const float4*>(b)[2 * i + 1];
     const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-    bf16x8_t s8, c8;
+    bf16x8 s8, c8;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         s8[j] = (bf16)(av[j] + bv[j]);
         c8[j] = (bf16)av[j];
     }
-    reinterpret_cast<bf16x8_t*>(sum)[i] = s8;
-    if (!ABF16 && ac) reinterpret_cast<bf16x8_t*>(ac)[i] = c8;
+    reinterpret_cast<bf16x8*>(sum)[i] = s8;
+    if (!ABF16 && ac) reinterpret_cast<bf16x8*>(ac)[i] = c8;
 }
 }  // namespace
 

@@ -34,18 +34,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
+#include "rowdrop.h"
 
 namespace {
 
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
+using rowdrop::mix32;
 
 constexpr int D = 64;     // head dim
 constexpr int KB = 64;    // keys per LDS tile
@@ -87,15 +81,6 @@ struct AttnArgs {
     unsigned long long* stamp;   // in-kernel launch stamps (measurement) or null: ov3d_stamps_arm
 };
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // per (seed, site, b*H+h) scalar mix; per query base; per (query, key) hash
 __device__ __forceinline__ uint32_t drop_head_mix(const int64_t* seed, uint32_t site, uint32_t bh) {
     const uint64_t s = (uint64_t)*seed;
@@ -123,11 +108,6 @@ __device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
 // high half the odd key; keep iff int16(half) >= thresh - 32768 (thresh = round(p * 2^16)),
 // i.e. (half ^ 0x8000) >= thresh unsigned
 constexpr uint32_t kPairMul = 0x27D4EB2Fu;
-
-// two fp32 -> two bf16 in one dword (one v_cvt_pk_bf16_f32), the even key in the low half
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){a, b}, bf16x2));
-}
 
 // 0xFFFF in each 16-bit half of the pair hash whose key is DROPPED: a saturating packed
 // subtract of the signed threshold leaves the sign of (half - tsig), an arithmetic shift
@@ -250,16 +230,6 @@ __device__ unsigned long long* g_attn_probe;
 #define PROBE_END do { } while (0)
 #endif
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
-
 // A operand of O^T += V^T P^T for d-tile dt and key k-step (t, s): lane (r = d, h)
 // element j = V[32t + 16s + 8(j>>2) + 4h + (j&3)][32dt + r]  (see header)
 __device__ __forceinline__ bf16x8 v_operand(const bf16* Vs, int lane, int dt, int t, int s) {
@@ -268,10 +238,7 @@ __device__ __forceinline__ bf16x8 v_operand(const bf16* Vs, int lane, int dt, in
     const int k0 = 32 * t + 16 * s + 4 * (g >> 1) + (i >> 2);
     const bf16x4 lo = tr16(Vs + img(k0, d0));
     const bf16x4 hi = tr16(Vs + img(k0 + 8, d0));
-    bf16x8 a;
-    a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
-    a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
-    return a;
+    return join8(lo, hi);
 }
 
 // 0xFFFFFFFF where bit b of w is set, else 0 (one v_bfe_i32; written as asm so that the

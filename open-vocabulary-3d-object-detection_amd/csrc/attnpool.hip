@@ -20,14 +20,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TP = 96;     // token rows (ntok + 1 <= TP), padded with zeros
 constexpr int HP = 48;     // head rows (H <= HP), padded with zeros
@@ -46,15 +41,6 @@ struct PoolArgs {
     int R, ntok, C, H;
 };
 
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
-
 // bf16(x + p) element-wise on one 16-byte run (fp32 add, one rounding: x + pos of the token rows)
 __device__ __forceinline__ uint4 add_bf16x8(uint4 xa, uint4 pa) {
     const bf16x8 xv = __builtin_bit_cast(bf16x8, xa), pv = __builtin_bit_cast(bf16x8, pa);
@@ -62,17 +48,6 @@ __device__ __forceinline__ uint4 add_bf16x8(uint4 xa, uint4 pa) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (bf16)((float)xv[e] + (float)pv[e]);
     return __builtin_bit_cast(uint4, o);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // One chunk's global loads, held in registers while the previous chunk computes.  Thread

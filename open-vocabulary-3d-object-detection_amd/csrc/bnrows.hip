@@ -17,12 +17,11 @@
 // Dropout keep(r, c) is a counter-based hash of (seed, site, r, c): the backward
 // regenerates the mask instead of storing it.
 #include "common.h"
+#include "mfma.h"
 #include "rowdrop.h"
+#include "rowsum.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct RowsLayout {
     long long ld, bstride;
@@ -53,22 +52,16 @@ __device__ __forceinline__ Phase phase(int C) {
     return p;
 }
 
-template <typename T>
-__device__ __forceinline__ void load8(const T* base, const RowsLayout& L, long long r, int c, float* v);
-template <>
-__device__ __forceinline__ void load8<bf16>(const bf16* base, const RowsLayout& L, long long r, int c,
-                                            float* v) {
-    const bf16x8 x = *reinterpret_cast<const bf16x8*>(base + addr(L, r, c));
+// 8 channels at element offset off of bf16 or fp32 rows, as fp32
+__device__ __forceinline__ void load8o(const bf16* base, long long off, float* v) {
+    const bf16x8 x = *reinterpret_cast<const bf16x8*>(base + off);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (float)x[j];
 }
-template <>
-__device__ __forceinline__ void load8<float>(const float* base, const RowsLayout& L, long long r,
-                                             int c, float* v) {
-    const float4 a = *reinterpret_cast<const float4*>(base + addr(L, r, c));
-    const float4 b = *reinterpret_cast<const float4*>(base + addr(L, r, c) + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+__device__ __forceinline__ void load8o(const float* base, long long off, float* v) { ld8f(base + off, v); }
+template <typename T>
+__device__ __forceinline__ void load8(const T* base, const RowsLayout& L, long long r, int c, float* v) {
+    load8o(base, addr(L, r, c), v);
 }
 
 // reduce the two per-thread accumulators over the RP row phases of the block and write
@@ -147,28 +140,6 @@ __device__ __forceinline__ long long coff(const RowsLayout& L, int c) {
     return (long long)(c / L.cb) * L.bstride + (c % L.cb);
 }
 
-template <typename T>
-__device__ __forceinline__ void load8o(const T* base, long long off, float* v);
-template <>
-__device__ __forceinline__ void load8o<bf16>(const bf16* base, long long off, float* v) {
-    const bf16x8 x = *reinterpret_cast<const bf16x8*>(base + off);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)x[j];
-}
-template <>
-__device__ __forceinline__ void load8o<float>(const float* base, long long off, float* v) {
-    const float4 a = *reinterpret_cast<const float4*>(base + off);
-    const float4 b = *reinterpret_cast<const float4*>(base + off + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void ld8f(const float* p, float* v) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    const float4 b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
 // the run / rows of this thread: rows r0 + k * rstep (k < RPT), channel c
 struct Slab {
     int c;
@@ -218,7 +189,7 @@ __global__ void __launch_bounds__(256) rows_bn_apply_kernel(
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         const long long r = q.r0 + k * q.rstep;
-        if (r < R) load8o<T>(x, ox + r * L.ld, v[k]);
+        if (r < R) load8o(x, ox + r * L.ld, v[k]);
     }
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
@@ -240,7 +211,6 @@ __global__ void __launch_bounds__(256) rows_bn_apply_kernel(
 // the dz run (row r, channels c .. c+7): read, or (POOLED) rebuilt from the neighbour max-pool's
 // pooled gradient g (P, C) and arg rows (P, C) uint8 -- row r = p * S + s takes g[p] where
 // arg[p] == s, else 0 (exactly the dense gradient ov3d_nbr_max_bwd would have written)
-typedef uint8_t u8x8 __attribute__((ext_vector_type(8)));
 template <bool POOLED>
 __device__ __forceinline__ void load_dz(const bf16* dz, const RowsLayout& LZ, long long r, int c,
                                         const uint8_t* parg, int pS, int C, float* v) {
@@ -286,9 +256,9 @@ __global__ void __launch_bounds__(256) rows_bn_bwd_kernel(
         for (int k = 0; k < RPT; ++k) {
             const long long r = q.r0 + k * q.rstep;
             if (r < R) {
-                load8o<T>(x, ox + r * LX.ld, xv[k]);
+                load8o(x, ox + r * LX.ld, xv[k]);
                 if constexpr (POOLED) load_dz<true>(dz, LZ, r, c, parg, pS, C, zv[k]);
-                else load8o<bf16>(dz, oz + r * LZ.ld, zv[k]);
+                else load8o(dz, oz + r * LZ.ld, zv[k]);
             }
         }
 #pragma unroll

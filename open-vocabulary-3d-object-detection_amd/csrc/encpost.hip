@@ -36,18 +36,13 @@
 // as whole row pieces) and one weight chunk (N x 64 k); the next chunk's global loads are in
 // flight while the current one is multiplied.
 #include "common.h"
+#include "mfma.h"
 #include "rowdrop.h"
 #include "rowsum.h"
 
 #include <type_traits>
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C = 256;            // model width
 constexpr int F = 128;            // feed-forward width
@@ -65,14 +60,6 @@ constexpr int LDIB = C + 4, LDHB = F + 4, LDWB = C + 32, LDWBF = F + 32;
 constexpr int WSZ = C * LDW;      // = BK * LDWB; also the backward's RPP x 2 x 256 fp32 column terms
 static_assert(BK * LDWB <= WSZ && 16 * 2 * C * 2 <= WSZ && RMULT % FWD_BM == 0 && RMULT % BWD_BM == 0,
               "W chunk region");
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
 
 // The accumulators of a wave's NTL 32 x 32 blocks over a K-deep product.  QS: K in four
 // quarters, each its own chain from zero, summed (q0 + q1) + (q2 + q3).
@@ -136,29 +123,18 @@ __device__ __forceinline__ void mma_bwd(Chain<NTL, K, QS>& ch, const bf16* ap, c
     for (int s = 0; s < BK / 16; ++s) {
         const bf16x4 lo = *reinterpret_cast<const bf16x4*>(ap + 16 * s);
         const bf16x4 hi = *reinterpret_cast<const bf16x4*>(ap + 16 * s + 8);
-        const bf16x8 af = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const bf16x8 af = join8(lo, hi);
         bf16x8 wf[NTL];
 #pragma unroll
         for (int nt = 0; nt < NTL; ++nt) {
             const bf16x4 wl = tr16(wp + 16 * s * LW + 32 * nt);
             const bf16x4 wh = tr16(wp + (16 * s + 8) * LW + 32 * nt);
-            wf[nt] = bf16x8{wl[0], wl[1], wl[2], wl[3], wh[0], wh[1], wh[2], wh[3]};
+            wf[nt] = join8(wl, wh);
         }
 #pragma unroll
         for (int nt = 0; nt < NTL; ++nt) ch.acc[nt] = mfma(wf[nt], af, ch.acc[nt]);
         ch.close(chunk * (BK / 16) + s);
     }
-}
-
-__device__ __forceinline__ void ld8f(const float* p, float* v) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    const float4 b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void st8f(float* p, const float* v) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
 
 // ---------------------------------------------------------------- forward
@@ -544,7 +520,7 @@ __global__ __launch_bounds__(BM * 8, QS ? BM / 32 : BM / 16) void enc_post_bwd_k
         const bf16* sp = &img[r * LDHB + 8 * pc];
         const bf16x4 lo = *reinterpret_cast<const bf16x4*>(sp), hi = *reinterpret_cast<const bf16x4*>(sp + 4);
         *reinterpret_cast<bf16x8*>(a.d1 + (size_t)(m0 + r) * F + 8 * pc) =
-            bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            join8(lo, hi);
     }
 
     // ---- dx2 = bf16(d1 W1)
@@ -744,7 +720,7 @@ __global__ __launch_bounds__(BM * 8, QS ? BM / 32 : BM / 16) void enc_post_bwd_k
         const bf16* sp = &img[r * LDIB + 8 * pc];
         const bf16x4 lo = *reinterpret_cast<const bf16x4*>(sp), hi = *reinterpret_cast<const bf16x4*>(sp + 4);
         *reinterpret_cast<bf16x8*>(a.dout + (size_t)(m0 + r) * C + 8 * pc) =
-            bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            join8(lo, hi);
     }
 }
 

@@ -25,10 +25,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
@@ -203,17 +202,6 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 
-__device__ __forceinline__ float wave_fmin(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float wave_fmax(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
 __device__ __forceinline__ uint32_t spread3(uint32_t x) {  // 4 bits -> every 3rd bit
     x &= 0xf;
     x = (x | (x << 4)) & 0x0c3;
@@ -261,8 +249,8 @@ __global__ __launch_bounds__(kThreads) void fps_cull_kernel(const float* __restr
         }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_fmin(lo[a]);
-        hi[a] = wave_fmax(hi[a]);
+        lo[a] = wave_min(lo[a]);
+        hi[a] = wave_max(hi[a]);
     }
     if (lane == 0)
 #pragma unroll
@@ -365,8 +353,8 @@ __global__ __launch_bounds__(kThreads) void fps_cull_kernel(const float* __restr
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        wlo[a] = wave_fmin(wlo[a]);
-        whi[a] = wave_fmax(whi[a]);
+        wlo[a] = wave_min(wlo[a]);
+        whi[a] = wave_max(whi[a]);
     }
     const float x0 = p[0], y0 = p[1], z0 = p[2];
     float x1 = x0, y1 = y0, z1 = z0;
@@ -589,8 +577,8 @@ __global__ __launch_bounds__(kThreads) void fps_stream_kernel(const float* __res
         }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        lo[a] = wave_fmin(lo[a]);
-        hi[a] = wave_fmax(hi[a]);
+        lo[a] = wave_min(lo[a]);
+        hi[a] = wave_max(hi[a]);
     }
     if (lane == 0)
 #pragma unroll
@@ -695,7 +683,7 @@ __global__ __launch_bounds__(kThreads) void fps_stream_kernel(const float* __res
         for (int c = 0; c < kNCB; ++c)
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                const float lo = wave_fmin(cLo[c][a]), hi = wave_fmax(cHi[c][a]);
+                const float lo = wave_min(cLo[c][a]), hi = wave_max(cHi[c][a]);
                 if (lane == c) { qLo[a] = lo; qHi[a] = hi; }
             }
     }
@@ -737,8 +725,8 @@ __global__ __launch_bounds__(kThreads) void fps_stream_kernel(const float* __res
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {   // wave-uniform: scalar registers
-        aLo[a] = sgpr_f(wave_fmin(aLo[a]));
-        aHi[a] = sgpr_f(wave_fmax(aHi[a]));
+        aLo[a] = sgpr_f(wave_min(aLo[a]));
+        aHi[a] = sgpr_f(wave_max(aHi[a]));
     }
     __syncthreads();   // s_perm complete before any tie lookup
     // this wave's cluster-B slots through a buffer descriptor: scalar base + lane offset +
@@ -941,8 +929,6 @@ __device__ __forceinline__ unsigned long long xword(uint32_t v, uint32_t tag) {
     return ((unsigned long long)tag << 32) | v;
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 // 16-byte sc1 load (bypasses this CU's L1; served by the XCD's L2 when the line is there)
 __device__ __forceinline__ u32x4 load_sc1_x4(const void* p) {
     u32x4 r;
@@ -1052,8 +1038,8 @@ __global__ __launch_bounds__(kThreads) void fps_pair_kernel(const float* __restr
             }
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            lo[a] = wave_fmin(lo[a]);
-            hi[a] = wave_fmax(hi[a]);
+            lo[a] = wave_min(lo[a]);
+            hi[a] = wave_max(hi[a]);
         }
         if (lane == 0)
 #pragma unroll
@@ -1159,8 +1145,8 @@ __global__ __launch_bounds__(kThreads) void fps_pair_kernel(const float* __restr
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        wlo[a] = wave_fmin(wlo[a]);
-        whi[a] = wave_fmax(whi[a]);
+        wlo[a] = wave_min(wlo[a]);
+        whi[a] = wave_max(whi[a]);
     }
     __syncthreads();   // s_perm (this half's positions) complete before any tie lookup
     const float x0 = p[0], y0 = p[1], z0 = p[2];

@@ -39,13 +39,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 64;
 constexpr int HALF = 128 * BK * 2;   // bytes of one 128-row half of an operand K-step
@@ -76,11 +72,6 @@ struct Gemm256Args {
     unsigned long long* stamp;   // in-kernel launch stamps (bench.py's C5 roofline) or null
 };
 
-__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 // ds_read_b128 as an asm statement: hipcc would otherwise treat the LDS read as aliasing the
 // in-flight LDS-DMA and wait vmcnt(0) before it.  The result is unprotected until a wait
 // statement names it (lgkm_wait*).
@@ -95,13 +86,6 @@ __device__ __forceinline__ void lgkm_wait12(i32x4 (&a)[8], i32x4 (&b)[4]) {
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]),
                    "+v"(a[6]), "+v"(a[7]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])
-                 :
-                 : "memory");
-}
-__device__ __forceinline__ void lgkm_wait8(i32x4 (&a)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]),
-                   "+v"(a[6]), "+v"(a[7])
                  :
                  : "memory");
 }
@@ -146,11 +130,6 @@ __device__ __forceinline__ void read_b(i32x4 (&fb)[4], uint32_t p0, uint32_t p1)
 
 __device__ __forceinline__ void glds(__amdgpu_buffer_rsrc_t rs, char* lds, uint32_t voff) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, 0, 0, 0);
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const uint32_t n = bytes > 0x7fffffffLL ? 0x7fffffffu : (uint32_t)(bytes > 0 ? bytes : 0);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)n, 0x00020000);
 }
 
 template <bool CONV, bool TAIL>   // TAIL: K % 64 != 0 (its own instance: the checks cost registers)
@@ -476,7 +455,6 @@ __global__ void __launch_bounds__(512, 2) gemm256_kernel(Gemm256Args a) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) o[r] = fmaxf(o[r], 0.f);
                         }
-                        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
                         const bf16x2 lo = {(bf16)o[0], (bf16)o[1]}, hi = {(bf16)o[2], (bf16)o[3]};
                         pk[j] = make_uint2(__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi));
                     }

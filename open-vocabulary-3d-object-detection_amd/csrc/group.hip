@@ -11,6 +11,7 @@
 // ascending order exactly as the upstream sequential scan produces them, and the
 // wave stops at the first chunk that fills S slots.
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
@@ -44,7 +45,6 @@ __device__ __forceinline__ void load4(const float* __restrict__ p, int k0, int N
 // fmaf(dz, dz, fmaf(dy, dy, dx * dx))), and points past N are padded far away
 // (d2 = inf) instead of being masked.  A centroid whose S slots are full skips the tests;
 // the wave stops when all CPW are full.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <bool ALIGNED, int CPW>
 __global__ __launch_bounds__(64 * kBQWavesPerBlock) void ball_query_kernel(
@@ -213,17 +213,6 @@ __device__ __forceinline__ int bq_axis(float v, float lo, float inv, int dim) {
     return f < 0.f ? -1 : (f >= (float)dim ? dim : (int)f);
 }
 
-__device__ __forceinline__ float bq_wave_fmin(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float bq_wave_fmax(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-
 // the scene's points as PPT register slots per thread (point k = tid + 1024 i), all loads in
 // flight at once; PPT = 0: a loop over global memory per pass (N > 32768)
 template <int PPT>
@@ -270,7 +259,7 @@ __global__ __launch_bounds__(1024) void bq_cells_build_kernel(const float* __res
         hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
     });
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { lo[a] = bq_wave_fmin(lo[a]); hi[a] = bq_wave_fmax(hi[a]); }
+    for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
     if (lane == 0)
 #pragma unroll
         for (int a = 0; a < 3; ++a) { s_red[a][w] = lo[a]; s_red[3 + a][w] = hi[a]; }
@@ -371,12 +360,6 @@ __device__ __forceinline__ int wave_sort_asc(int v) {
             const bool low = (lane & j) == 0;
             v = (low == up) ? min(v, o) : max(v, o);
         }
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
 
@@ -690,7 +673,6 @@ __global__ __launch_bounds__(256) void group_rows_bf16_kernel(
     const float* __restrict__ feats, long long sb, long long sn, long long sc,
     const int32_t* __restrict__ idx, int B, int C, int N, int M, int S, float radius,
     int normalize, int ldo, __bf16* __restrict__ out) {
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     const int chunks = ldo >> 3;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long rows = (long long)B * M * S;
@@ -771,8 +753,6 @@ __global__ __launch_bounds__(256) void group_bwd_csr_kernel(const GT* __restrict
     gfeat[b * sb + n * sn + c * sc] = acc;
 }
 
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-
 // the same gather over bf16 rows with ldg % 8 == 0 and 16-byte aligned rows: a thread owns
 // the 16-byte chunk q of each row it reads (columns 8q .. 8q+7 = channels 8q-3 .. 8q+4), one
 // row id and one 16-byte load per entry instead of one of each per channel.  Each channel sums
@@ -798,11 +778,11 @@ __global__ __launch_bounds__(256) void group_bwd_csr_vec_kernel(const __bf16* __
     int e = e0;
     for (; e + 8 <= e1; e += 8) {
         int r[8];
-        bf16x8v v[8];
+        bf16x8 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) r[u] = rows[e + u];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const bf16x8v*>(g + (size_t)r[u] * ldg);
+        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const bf16x8*>(g + (size_t)r[u] * ldg);
 #pragma unroll
         for (int u = 0; u < 8; ++u)
 #pragma unroll
@@ -810,13 +790,13 @@ __global__ __launch_bounds__(256) void group_bwd_csr_vec_kernel(const __bf16* __
     }
     if (e < e1) {
         int r[8];
-        bf16x8v v[8];
+        bf16x8 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) r[u] = e + u < e1 ? rows[e + u] : -1;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             if (r[u] >= 0) {
-                v[u] = *reinterpret_cast<const bf16x8v*>(g + (size_t)r[u] * ldg);
+                v[u] = *reinterpret_cast<const bf16x8*>(g + (size_t)r[u] * ldg);
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[u][j] = (__bf16)0.f;

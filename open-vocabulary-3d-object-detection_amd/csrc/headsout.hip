@@ -25,13 +25,9 @@
 // gradients in bf16 and the box heads' input gradient dz2[:, 256 (1+i) + c] = sum_j g_i[j] W_i[j, c]
 // (n_out <= 32 terms, fp32) into its columns of the caller's dz2.
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int RB = 32;          // rows per workgroup
 constexpr int KH = 256;         // hidden width of every head
@@ -66,10 +62,6 @@ struct HeadsOutArgs {
 template <class T>
 __device__ __forceinline__ T pick4(const T (&v)[MAXS], int i) {
     return i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3];
-}
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
 // one 32-channel tile of rows z (this lane: row r, operand k-half h): acc[e] = channel

@@ -31,16 +31,11 @@
 // tile t == 0 workgroups also store the row pass's outputs (s, mean, rstd, xa, xap, xb /
 // dsrc, dy, dpos and the LayerNorm column partials in resnorm_bwd's per-8-row layout).
 #include "common.h"
+#include "mfma.h"
 #include "rowdrop.h"
 #include "rowsum.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C = 256;            // model width: the LayerNorm rows and the GEMMs' K / N
 constexpr int RB = 16;            // rows per workgroup
@@ -57,23 +52,6 @@ constexpr int CRB = C + 32;       // LayerNorm column terms: 4 pad dwords per 32
 __device__ __forceinline__ int redix(int row, int col) { return row * CRB + col + 4 * (col >> 5); }
 enum { EPI_NONE = 0, EPI_RELU_DROP = 1, EPI_MASK = 2 };
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
-__device__ __forceinline__ void st8f(float* p, long long off, const float* v) {
-    *reinterpret_cast<float4*>(p + off) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + off + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-__device__ __forceinline__ bf16x8 pack8(const float* v) {
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16)v[j];
-    return o;
-}
 // raw 8-channel row pieces: loaded early (every load of a row pass in flight at once),
 // converted at their use
 struct Raw8 {
@@ -516,11 +494,11 @@ __global__ void __launch_bounds__(NT) lngemm_bwd_kernel(LnBwdArgs a) {
             const int ks = 4 * kq + s4;
             const bf16x4 lo = *reinterpret_cast<const bf16x4*>(ar + 16 * ks + 4 * h);
             const bf16x4 hi = *reinterpret_cast<const bf16x4*>(ar + 16 * ks + 8 + 4 * h);
-            const bf16x8 av = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            const bf16x8 av = join8(lo, hi);
             const int k0 = 16 * ks + 4 * (gq >> 1) + (i16 >> 2);
             const bf16x4 wl = tr16(ws + k0 * LDWB + d0);
             const bf16x4 wh = tr16(ws + (k0 + 8) * LDWB + d0);
-            const bf16x8 bv = bf16x8{wl[0], wl[1], wl[2], wl[3], wh[0], wh[1], wh[2], wh[3]};
+            const bf16x8 bv = join8(wl, wh);
             acc = mfma(bv, av, acc);
         }
         if (r < RB) {

@@ -14,12 +14,9 @@
 // training BN without dropout), so z is never stored; its backward is the pooled-gradient mode
 // of ov3d_rows_bn_bwd (csrc/bnrows.hip), which rebuilds this dense gradient row by row.
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint8_t u8x8 __attribute__((ext_vector_type(8)));
 
 __global__ void __launch_bounds__(256) nbr_max_fwd_kernel(const bf16* __restrict__ y, long long P,
                                                           int S, int C, bf16* __restrict__ out,

@@ -24,14 +24,9 @@
 //   * tiles are claimed from a counter, so a late workgroup (a side-stream kernel holding CUs,
 //     e.g. the next step's furthest-point sampling) does not add a tail round of its own.
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 512;                 // threads
 constexpr int TM = 128;                 // rows a tile
@@ -40,11 +35,6 @@ constexpr int TILE_BYTES = TM * KD * 2; // 64 KB
 constexpr int RB = TM / 16;             // 16-row blocks a tile
 constexpr int TAIL_BYTES = TM * 16;     // KT: the K = 256 .. 263 chunk of a tile's rows
 constexpr int WX_BYTES = 16 * KD * 2;   // NX: W rows 256 .. 271 (zeros past 263), swizzled
-
-__device__ __forceinline__ f32x4 mfma16(i32x4 a, i32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 
 // ds_read_b128 as asm: the compiler would treat an LDS read as aliasing the in-flight
 // LDS-DMA and wait for every load (vmcnt(0)) before it.  Results are consumed only after
@@ -58,13 +48,6 @@ __device__ __forceinline__ i32x4 lds128(uint32_t addr) {
 __device__ __forceinline__ void lds_write64(uint32_t addr, bf16x4 v) {
     asm volatile("ds_write_b64 %0, %1" : : "v"(addr), "v"(v) : "memory");
 }
-__device__ __forceinline__ void lgkm_wait8(i32x4 (&a)[RB]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]),
-                   "+v"(a[6]), "+v"(a[7])
-                 :
-                 : "memory");
-}
 
 // atomicAdd(ctr, 1) as asm: the compiler would wait for its result (vmcnt(0), i.e. the previous
 // tile's stores too) at the join of the lane-0 branch.  Untracked by the compiler's wait counts
@@ -76,11 +59,6 @@ __device__ __forceinline__ unsigned int claim_async(unsigned int* ctr) {
                  : "v"(ctr), "v"(1u)
                  : "memory");
     return r;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long long bytes) {
-    const uint32_t n = bytes > 0x7fffffffLL ? 0x7fffffffu : (uint32_t)(bytes > 0 ? bytes : 0);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)n, 0x00020000);
 }
 
 struct Rows256Args {

@@ -22,15 +22,10 @@
 //   EPI_MASK:      out = h > 0 ? bf16(bf16(acc) / (1 - p)) : 0   (the input gradient of
 //                  linear2 through that activation, as ov3d_relu_dropout_bwd)
 #include "common.h"
+#include "mfma.h"
 #include "rowdrop.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWaves = 4;
 constexpr int kTile = 32;
@@ -47,16 +42,6 @@ struct GemmArgs {
     int epi; uint32_t thresh; float keep_scale; const int64_t* seed; uint32_t site;
     const bf16* H; long long ldh;   // EPI_MASK: the activation output
 };
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
 
 // One 32 x 32 output tile (m0, n0) of problem a; K = 4 waves x 16 x `steps` (<= STEPS).
 template <int TB, int STEPS>
@@ -95,7 +80,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int m0, int n0, int
             if (s < steps) {
                 const bf16x4 lo = *reinterpret_cast<const bf16x4*>(ap + 16 * s + 4 * h);
                 const bf16x4 hi = *reinterpret_cast<const bf16x4*>(ap + 16 * s + 8 + 4 * h);
-                av[s] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                av[s] = join8(lo, hi);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -112,7 +97,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int m0, int n0, int
                 const int k0 = 16 * s + 4 * (g >> 1) + (i >> 2);
                 const bf16x4 lo = tr16(ws + k0 * LDW + d0);
                 const bf16x4 hi = tr16(ws + (k0 + 8) * LDW + d0);
-                bv[s] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                bv[s] = join8(lo, hi);
             }
         }
     }

@@ -21,14 +21,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = 64;      // rows per tile (one centroid at S = 64, two at S = 32)
 constexpr int kThreads = 256;  // 4 waves
@@ -77,16 +72,6 @@ __device__ __forceinline__ int lane_fresh() {
     return l;
 }
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
-
 // MFMA operand whose lane index runs over the columns c0 .. c0+31 of a row-major LDS tile
 // and whose 8 elements are rows 16s + 8(j>>2) + 4h + (j&3) (ds_read_b64_tr_b16; the two
 // operands of one product use the same row order)
@@ -96,7 +81,7 @@ __device__ __forceinline__ bf16x8 col_operand(const bf16* T, int ld, int lane, i
     const int k0 = 16 * s + 4 * (g >> 1) + (i >> 2);
     const bf16x4 lo = tr16(T + k0 * ld + d0);
     const bf16x4 hi = tr16(T + (k0 + 8) * ld + d0);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return join8(lo, hi);
 }
 
 template <int K, int N, bool STATS>
@@ -294,7 +279,7 @@ __global__ __launch_bounds__(kThreads, 1) void sa_dy_fused_kernel(DyFusedArgs p)
                 const bf16* dn = DsT + (wave * (N / 4) + 32 * a + r32) * LDR + 16 * s + 4 * h;
                 const bf16x4 lo = *reinterpret_cast<const bf16x4*>(dn);
                 const bf16x4 hi = *reinterpret_cast<const bf16x4*>(dn + 8);
-                const bf16x8 ad = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const bf16x8 ad = join8(lo, hi);
 #pragma unroll
                 for (int b = 0; b < WK; ++b) dw[a][b] = mfma(ad, bz[b], dw[a][b]);
             }
@@ -573,11 +558,11 @@ __global__ __launch_bounds__(512, 1) void sa_dy9_kernel(DyFusedArgs p) {
             auto ld = [&](int s) __attribute__((always_inline)) {
                 const bf16x4 lo = tr16(zlo[s & 1] + 16 * LDR * s);
                 const bf16x4 hi = tr16(zhi[s & 1] + 16 * LDR * s);
-                aq[s] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                aq[s] = join8(lo, hi);
                 if (s < NWL) {
                     const bf16x4 wl = tr16(W3s + (xlo ^ kbz) + 16 * K * s);
                     const bf16x4 wh = tr16(W3s + (xhi ^ kbz) + 16 * K * s);
-                    wt[s] = bf16x8{wl[0], wl[1], wl[2], wl[3], wh[0], wh[1], wh[2], wh[3]};
+                    wt[s] = join8(wl, wh);
                 }
             };
 #pragma unroll
@@ -606,11 +591,11 @@ __global__ __launch_bounds__(512, 1) void sa_dy9_kernel(DyFusedArgs p) {
                 if (b == 0) {
                     const bf16x4 lo = *reinterpret_cast<const bf16x4*>(&DsT[oy ^ (16 * s)]);
                     const bf16x4 hi = *reinterpret_cast<const bf16x4*>(&DsT[oy ^ 8 ^ (16 * s)]);
-                    adq[s] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    adq[s] = join8(lo, hi);
                 }
                 const bf16x4 lo = tr16(As + (xlo ^ (32 * b)) + 16 * K * s);
                 const bf16x4 hi = tr16(As + (xhi ^ (32 * b)) + 16 * K * s);
-                bzq[t] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                bzq[t] = join8(lo, hi);
             };
             constexpr int NT = kTile / 16 * (K / 32);
             static_assert(NT == 16, "one dz element per dW3 product");
@@ -878,12 +863,12 @@ __global__ __launch_bounds__(kThreads, 1) void sa_dy2_fused_kernel(Dy2Args p) {
 #pragma unroll
         for (int s = 0; s < kTile / 16; ++s) {
             const bf16x4 dl = tr16(Ds + dlo + 16 * N * s), dh = tr16(Ds + dhi + 16 * N * s);
-            const bf16x8 ad = bf16x8{dl[0], dl[1], dl[2], dl[3], dh[0], dh[1], dh[2], dh[3]};
+            const bf16x8 ad = join8(dl, dh);
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
                 const bf16x4 al = tr16(As + (alo ^ (32 * b)) + 16 * K * s);
                 const bf16x4 ah = tr16(As + (ahi ^ (32 * b)) + 16 * K * s);
-                dw[b] = mfma(ad, bf16x8{al[0], al[1], al[2], al[3], ah[0], ah[1], ah[2], ah[3]}, dw[b]);
+                dw[b] = mfma(ad, join8(al, ah), dw[b]);
             }
         }
         if constexpr (X0) {   // the next tile's x0 (its prologue reads it after the barrier)

@@ -30,20 +30,10 @@
 #include <limits.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
 
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-// two fp32 -> two bf16 in one dword (one v_cvt_pk_bf16_f32), the first in the low half
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){a, b}, bf16x2));
-}
 // the two bf16 halves of a dword as fp32 (exact)
 __device__ __forceinline__ f32x2 unpack_bf16(uint32_t u) {
     return f32x2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
@@ -230,7 +220,7 @@ __global__ __launch_bounds__(kThreads, 2) void sa_layer_kernel(LayerArgs p) {
                 const bf16x8 a = *reinterpret_cast<const bf16x8*>(&As[(rb * 32 + r32) * LDK + 16 * s + 8 * h]);
 #pragma unroll
                 for (int cb = 0; cb < NB; ++cb)
-                    acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfrag[cb][s], acc[rb][cb], 0, 0, 0);
+                    acc[rb][cb] = mfma(a, bfrag[cb][s], acc[rb][cb]);
             }
         }
         if constexpr (X0) {   // the next tile's x0 (its prologue reads it after the barrier)

@@ -65,11 +65,6 @@ __device__ __forceinline__ void softmax_stats(const float* x, int n, float& mx, 
     for (int t = 0; t < n; ++t) s += expf(x[t] - mx);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the loss terms of proposal p of computation layer l into acc (sem num, sem den, angle cls,
 // angle reg, center, size, giou) and the scene's count of non-background argmax (cnt, LDS)
 __device__ __forceinline__ void proposal_terms(const ov3d_set_loss_desc& d, int l, int p, int P,

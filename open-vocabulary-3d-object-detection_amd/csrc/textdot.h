@@ -12,9 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "mfma.h"
 
 constexpr int kChunk = 128;      // bytes of a row per K-chunk
 constexpr int kStride = 136;     // LDS row pitch in bytes

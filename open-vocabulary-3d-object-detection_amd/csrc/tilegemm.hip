@@ -27,6 +27,7 @@
 //   EPI_MASK:      out = h > 0 ? bf16(bf16(acc) / (1 - p)) : 0   (linear2's input gradient
 //                  through that activation, h = the activation output)
 #include "common.h"
+#include "mfma.h"
 #include "rowdrop.h"
 
 #include <stdlib.h>
@@ -34,12 +35,6 @@
 #include <type_traits>
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BN = 128, BK = 64;
 constexpr int KALIGN = BK;
@@ -65,15 +60,6 @@ struct TileArgs {
     // batched products (ov3d_tile_gemm_batched): grid.y = batch, element strides per batch
     long long sA, sW, sC;
 };
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
 
 template <int TB, int BM, int NWV = 4>
 struct Tile {
@@ -225,7 +211,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void tile_gemm_kernel(TileArgs p) {
                 } else {
                     const bf16x4 lo = *reinterpret_cast<const bf16x4*>(ar + 4 * h);
                     const bf16x4 hi = *reinterpret_cast<const bf16x4*>(ar + 8 + 4 * h);
-                    af[mt] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    af[mt] = join8(lo, hi);
                 }
             }
 #pragma unroll
@@ -239,7 +225,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void tile_gemm_kernel(TileArgs p) {
                     const int k0 = 16 * s + 4 * (g >> 1) + (i >> 2);
                     const bf16x4 lo = tr16(&Ws[k0 * T::LDW + d0]);
                     const bf16x4 hi = tr16(&Ws[(k0 + 8) * T::LDW + d0]);
-                    wf[nt] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    wf[nt] = join8(lo, hi);
                 }
             }
 #pragma unroll

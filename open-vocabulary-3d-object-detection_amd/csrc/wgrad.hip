@@ -29,14 +29,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TN = 128, TK = 128;  // output tile (rows of dW = N, cols = K)
 constexpr int RS = 32;             // rows of dy / x per LDS stage
@@ -60,15 +55,6 @@ struct WgradArgs {
     const float* xh;
 };
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ bf16x4 tr16(const bf16* p) {
-    s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-    return __builtin_bit_cast(bf16x4, r);
-}
-
 // operand fragment of a 32-column slice c0 of a [RS][LDT] tile for k-step ks (16 rows):
 // lane (col = c0 + (lane & 31), half h) gets rows 16ks + 8h + j, j = 0..7
 __device__ __forceinline__ bf16x8 col_frag(const bf16* T, int lane, int c0, int ks) {
@@ -77,10 +63,7 @@ __device__ __forceinline__ bf16x8 col_frag(const bf16* T, int lane, int c0, int 
     const int row = 16 * ks + 8 * (g >> 1) + (i >> 2);
     const bf16x4 lo = tr16(T + row * LDT + col);
     const bf16x4 hi = tr16(T + (row + 4) * LDT + col);
-    bf16x8 a;
-    a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
-    a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
-    return a;
+    return join8(lo, hi);
 }
 
 // ------------------------------------------------------------- 256 x 256 tiles, 8 waves
@@ -651,7 +634,6 @@ __global__ void __launch_bounds__(64) wgrad_group_table_kernel(WgradWrite w) {
 // The table is written by earlier launches and only read here: reads through the constant
 // address space stay scalar loads (the index is workgroup-uniform).
 #define SK_CONST __attribute__((address_space(4)))
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ WgradSK sk_rec(const WgradSK* rec, int i) {
     struct { i32x4 q[4]; } v;
     const SK_CONST i32x4* p = (const SK_CONST i32x4*)(uintptr_t)(rec + i);
